@@ -7,8 +7,14 @@ stream (seed 1729 + rank): weak scaling, no data-path collective; RCCL only gath
 digests to rank 0 after the timed region (the trivial frame gather).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--gops G] [--config c1|c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (see DESIGN.md
+"Measurement"): frames/s, ms_per_step and the roofline fraction of the timed steps.  --full adds
+everything that takes runs or checks of its own: parity of every frame against the compiled
+reference's digests, the one-stream per-kernel roofline, the shader clock probe, the rank-0 frame
+gather (N > 1), the CPU baseline and the drop-in end-to-end lines.  --dump-outputs DIR writes what
+the last timed step decoded as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -43,8 +49,9 @@ def spawn_ranks_if_needed(argv):
         return
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--prepare", action="store_true")
     known, _ = ap.parse_known_args(argv)
-    if known.gpus <= 1:
+    if known.gpus <= 1 or known.prepare:  # --prepare writes every rank's stream from one process
         return
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={known.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + list(argv)
@@ -140,6 +147,78 @@ def expected_digests(config, gops, seed):
         return d[key].copy() if key in d else None
 
 
+def _library_stamp():
+    """Content stamp of the library this process loads (build.py writes it beside the .so), or None."""
+    from tiny_mp2v_dec_amd import _lib
+    try:
+        with open(_lib.LIB_PATH + ".stamp") as fh:
+            return fh.read().strip() or None
+    except OSError:
+        return None
+
+
+def bench_stream(config, gops, seed):
+    """The elementary stream of (config, gops, seed).  Writing 3,072 1080p frames takes the
+    single-threaded generator tens of seconds, so the stream is kept under
+    tiny_mp2v_dec_amd/_build/bench_streams/, keyed by its parameters and by the stamp of the library
+    that wrote it (a changed generator never reads an old stream); `bench.py --prepare`, which
+    build() runs, writes the default workload's, and any other is written by the first run that
+    needs it.  Without a stamp (a library built by hand) the stream is generated every time."""
+    width, height, cf, gparams, _ = CONFIGS[config]
+    stamp = _library_stamp()
+    path = None
+    if stamp is not None:
+        d = os.path.join(REPO, "tiny_mp2v_dec_amd", "_build", "bench_streams")
+        path = os.path.join(d, f"{config}_g{gops}_s{seed}_{stamp[:16]}.m2v")
+        try:
+            with open(path, "rb") as fh:
+                return fh.read()
+        except OSError:
+            pass
+    es = R.generate_es(width=width, height=height, chroma_format=cf, n_gops=gops, seed=seed, **gparams)
+    if path is not None:
+        tmp = f"{path}.{os.getpid()}.tmp"
+        try:
+            os.makedirs(d, exist_ok=True)
+            for old in os.listdir(d):  # the same stream written by an earlier build of the library
+                if old.startswith(f"{config}_g{gops}_s{seed}_") and old.endswith(".m2v"):
+                    os.unlink(os.path.join(d, old))
+            with open(tmp, "wb") as fh:
+                fh.write(es)
+            os.replace(tmp, path)
+        except OSError as e:  # a read-only or full tree: the run goes on with the stream in memory
+            print(f"bench.py: stream not kept ({e})", file=sys.stderr)
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+    return es
+
+
+DUMP_BUDGET = 56 << 20  # bytes of sampled frames per rank (--dump-outputs stays below 64 MB in all)
+
+
+def dump_outputs(ctx, parsed, out_dir, rank):
+    """--dump-outputs: what the last timed step left in the frame pool, as float32 / float64 .npy.
+    frames_y / frames_u / frames_v: the visible planes of a fixed sample of frames (seed 1729,
+    as many whole frames as fit DUMP_BUDGET; (k, rows, columns) float32), frame_slots: their decode
+    indices, frame_digests: the device digest of EVERY frame as (npics, 2) float64, high and low 32
+    bits, so that two builds compare over the whole batch.  Rank r > 0 appends _rank<r> to each name."""
+    per_frame = 4 * ctx.frame_bytes()
+    if per_frame > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: one {per_frame}-byte float32 frame exceeds the {DUMP_BUDGET}-byte budget")
+    k = min(parsed.npics, DUMP_BUDGET // per_frame)
+    slots = np.sort(np.random.default_rng(1729).choice(parsed.npics, size=k, replace=False))
+    frames = [ctx.download(int(s)) for s in slots]
+    dig = ctx.digests(np.arange(parsed.npics))
+    arrays = {"frame_slots": slots.astype(np.float64),
+              "frame_digests": np.stack([dig >> np.uint64(32), dig & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)}
+    for i, name in enumerate(("frames_y", "frames_u", "frames_v")):
+        arrays[name] = np.stack([f[i] for f in frames]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def cpu_baseline(es, width, height, cf, frames):
     """The REAL reference (oracle/_ref/ref_decode, x86 SSE2, its own multithreaded path) on the
     same stream, timed on this host.  Falls back to the oracle C port when the prebuilt
@@ -196,6 +275,8 @@ def init_distributed(backend):
     set first and the process group is bound to it (device_id: eager communicator init), and the
     collectives move cuda tensors; gloo: CPU tensors (several ranks may share one GPU).
     Returns (rank, world, dist or None, collective device, local GPU index)."""
+    if "WORLD_SIZE" not in os.environ:  # no launcher: one rank on GPU 0, and torch is never imported
+        return 0, 1, None, "cpu", 0
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -300,12 +381,27 @@ def main():
                          "share one GPU to rehearse the multi-GPU path)")
     ap.add_argument("--gather-gops", type=int, default=8,
                     help="GOPs per rank in the rank-0 frame gather measured after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the drop-in end-to-end measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check every frame against the reference's digests and "
+                         "measure the one-stream per-kernel roofline, the shader clock, the rank-0 frame gather "
+                         "(N > 1), the CPU baseline and the drop-in end to end")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step decoded as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--prepare", action="store_true",
+                    help="write each rank's stream under tiny_mp2v_dec_amd/_build/ and exit (no GPU; build() "
+                         "runs this so that a benchmark run does not spend its time generating the stream)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the drop-in end-to-end measurement")
     ap.add_argument("--probe-launch", action="store_true",
                     help="form the process group, check world == --gpus with one all_reduce, print one JSON "
                          "line and exit before any GPU work (CPU test of the N-rank launch)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.prepare:
+        for r in range(args.gpus):
+            bench_stream(args.config, args.gops or DEFAULT_GOPS[args.config], 1729 + r)
+        return
 
     rank, world, dist, coll_dev, device = init_distributed(args.backend)
     if world != args.gpus:
@@ -320,8 +416,6 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    import torch
-
     if rank == 0:
         _build.build()
     if dist is not None:
@@ -329,12 +423,12 @@ def main():
 
     from tiny_mp2v_dec_amd import gather as G
 
-    width, height, cf, gparams, desc = CONFIGS[args.config]
+    width, height, cf, _, desc = CONFIGS[args.config]
     # c5 is I-only: one picture per "GOP", so --gops is its frame count (~60 frames; at
     # 768 frames its elementary stream would pass the 2 GB `int len` of the reference decode() API)
     gops = args.gops or DEFAULT_GOPS[args.config]
     seed = 1729 + rank
-    es = R.generate_es(width=width, height=height, chroma_format=cf, n_gops=gops, seed=seed, **gparams)
+    es = bench_stream(args.config, gops, seed)
     parsed = R.Parsed(es, width, height, cf, threads=min(8, os.cpu_count() or 1))
     alg_bytes, parts = algorithmic_bytes(parsed)
     ctx = R.DeviceContext(width, height, cf, slots=parsed.npics, device=device)
@@ -342,7 +436,7 @@ def main():
     # the one-stream context of the per-kernel lines (used after the timed region); with
     # MP2VG_BENCH_CTX1_EARLY=1 (measurements) it takes its pool now, before ctx's first batch
     ctx1 = None
-    if os.environ.get("MP2VG_BENCH_CTX1_EARLY") == "1":
+    if args.full and os.environ.get("MP2VG_BENCH_CTX1_EARLY") == "1":
         ctx1 = R.DeviceContext(width, height, cf, slots=parsed.npics, device=device, one_stream=True)
         ctx1.upload(parsed.pics, parsed.mbs, parsed.coefs)
 
@@ -375,8 +469,96 @@ def main():
     device_span_ms = ctx.batches_span(timed - 1, 0)
     # the runtime's pool placement calibration at the context's first (warm-up) batch
     place_ms, place_kept = ctx.placement()
-    elapsed = G.max_over_ranks(elapsed, dist, coll_dev)
+    if dist is not None:
+        elapsed = G.max_over_ranks(elapsed, dist, coll_dev)
 
+    full = None
+    if args.full:
+        full = full_measurements(args, rank, dist, coll_dev, device, ctx, ctx1, parsed, gops, seed)
+    if args.dump_outputs:
+        dump_outputs(ctx, parsed, args.dump_outputs, rank)
+    ctx.close()
+
+    traffic = profiled_traffic(args.config, gops)
+    frames_total = parsed.npics * world * args.steps
+    ms_per_step = elapsed * 1000.0 / args.steps
+    per_launch = [x for step in kernel_ms for x in step]
+    # the kernel time of a step: the device span of the timed steps (HIP events on the launch
+    # streams, first batch start -> last batch end, gaps between launches included) / steps
+    kernel_step_ms = device_span_ms / timed
+    achieved = alg_bytes / (kernel_step_ms / 1000.0) / 1e9
+    result = {
+        "metric": BASELINE_METRIC,
+        "value": round(frames_total / elapsed, 1),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": f"{desc}, pre-parsed MB records resident in HBM, {gops} GOPs per GPU",
+                   "width": width, "height": height, "chroma_format": {1: "4:2:0", 2: "4:2:2", 3: "4:4:4"}[cf],
+                   "frames_per_gpu_per_step": parsed.npics, "global_batch_frames": parsed.npics * world,
+                   "parallelism": f"gop-shard x{world}", "backend": args.backend if dist is not None else None},
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic["traffic_bytes_per_step"] if traffic else None,
+                     "traffic_unit": "bytes/step (HBM, PMC)", "traffic_source": traffic["source"] if traffic else None,
+                     "traffic_fetch_raw": traffic.get("fetch_raw_bytes_per_step") if traffic else None,
+                     "traffic_write": traffic.get("write_bytes_per_step") if traffic else None,
+                     "l2_requests_per_step": traffic.get("l2_requests_per_step") if traffic else None,
+                     "l2_hit_rate": traffic.get("l2_hit_rate") if traffic else None,
+                     # on-chip bound: L1->L2 request bytes over the algorithmic bytes, at 64 B per
+                     # request (the sector a 20-B tap row or a 64-B store quad needs) and at the
+                     # 128-B line a read request fills (tools/fetch_calib.hip): lower / upper bound
+                     "l1l2_amplification": (round(traffic["l2_requests_per_step"] * 64 / alg_bytes, 3)
+                                            if traffic and traffic.get("l2_requests_per_step") else None),
+                     "l1l2_amplification_128B": (round(traffic["l2_requests_per_step"] * 128 / alg_bytes, 3)
+                                                 if traffic and traffic.get("l2_requests_per_step") else None),
+                     "kernel": "mp2vg::recon_kernel", "launches_per_step": len(kernel_ms[0]),
+                     "avg_launch_ms": round(float(np.mean(per_launch)), 4),
+                     "algorithmic_bytes_per_step": int(alg_bytes), "bytes_breakdown": parts,
+                     "kernel_ms_per_step": round(kernel_step_ms, 4),
+                     "batch_span_ms": round(float(np.mean(batch_ms)), 4),
+                     "sum_launch_ms_per_step": round(float(np.mean([sum(s) for s in kernel_ms])), 4)},
+        "box": {"host_cpus_visible": os.cpu_count()},
+        "pool_placement": {"candidate_batch_ms": place_ms, "kept": place_kept,
+                           "note": "runtime.cpp calibrate_placement, at the first warm-up batch: the batch "
+                                   "decoded on the pool and on copies in fresh blocks (round 0 of each, then "
+                                   "round 1), the fastest pool kept; outside the timed region"},
+        "provenance": _build.provenance(),
+    }
+    parity = None
+    if full is not None:
+        parity = result["parity"] = full["parity"]
+        result["roofline"].update(full["roofline"])
+        result["box"]["shader_clock_ghz_valu_load"] = full["clock_ghz"]
+        result["frame_digest_of_digests"] = full["frame_digest_of_digests"]
+        if full["frame_gather"] is not None:
+            result["frame_gather"] = full["frame_gather"]
+        if rank == 0 and world == 1 and dist is None and not args.no_cpu_baseline:
+            result["cpu_baseline"] = cpu_baseline(es, width, height, cf, parsed.npics)
+        if rank == 0 and world == 1 and dist is None and not args.no_e2e:
+            result["e2e_dropin"] = e2e_dropin(es, width, height, cf, parsed.npics, device,
+                                              result.get("cpu_baseline"))
+            result["e2e_dropin_device_frames"] = e2e_dropin(es, width, height, cf, parsed.npics, device,
+                                                            result.get("cpu_baseline"), device_frames=True)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+    if parity is not None and parity["status"] == "MISMATCH":
+        sys.exit(3)
+
+
+def full_measurements(args, rank, dist, coll_dev, device, ctx, ctx1, parsed, gops, seed):
+    """--full: what the bench line reports beyond the timed steps and takes device work of its own,
+    run after the timed region on the batch the last step decoded.  ctx1: the one-stream context
+    when it was created early (MP2VG_BENCH_CTX1_EARLY), else None."""
+    width, height, cf = parsed.width, parsed.height, parsed.chroma_format
     # ---- parity of the timed batch: device digest of every frame vs the compiled reference's ----
     dig = ctx.digests(np.arange(parsed.npics))
     exp = expected_digests(args.config, gops, seed)
@@ -428,78 +610,9 @@ def main():
     ghz = ctypes.c_double(0.0)
     clock_ghz = round(ghz.value, 3) if _native().mp2vg_clock_probe(device, ctypes.byref(ghz)) == 0 else None
 
-    traffic = profiled_traffic(args.config, gops)
-    frames_total = parsed.npics * world * args.steps
-    ms_per_step = elapsed * 1000.0 / args.steps
-    per_launch = [x for step in kernel_ms for x in step]
-    # the kernel time of a step: the device span of the timed steps (HIP events on the launch
-    # streams, first batch start -> last batch end, gaps between launches included) / steps
-    kernel_step_ms = device_span_ms / timed
-    achieved = alg_bytes / (kernel_step_ms / 1000.0) / 1e9
-    result = {
-        "metric": BASELINE_METRIC,
-        "value": round(frames_total / elapsed, 1),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": f"{desc}, pre-parsed MB records resident in HBM, {gops} GOPs per GPU",
-                   "width": width, "height": height, "chroma_format": {1: "4:2:0", 2: "4:2:2", 3: "4:4:4"}[cf],
-                   "frames_per_gpu_per_step": parsed.npics, "global_batch_frames": parsed.npics * world,
-                   "parallelism": f"gop-shard x{world}", "backend": args.backend if dist is not None else None},
-        "parity": parity,
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic["traffic_bytes_per_step"] if traffic else None,
-                     "traffic_unit": "bytes/step (HBM, PMC)", "traffic_source": traffic["source"] if traffic else None,
-                     "traffic_fetch_raw": traffic.get("fetch_raw_bytes_per_step") if traffic else None,
-                     "traffic_write": traffic.get("write_bytes_per_step") if traffic else None,
-                     "l2_requests_per_step": traffic.get("l2_requests_per_step") if traffic else None,
-                     "l2_hit_rate": traffic.get("l2_hit_rate") if traffic else None,
-                     # on-chip bound: L1->L2 request bytes over the algorithmic bytes, at 64 B per
-                     # request (the sector a 20-B tap row or a 64-B store quad needs) and at the
-                     # 128-B line a read request fills (tools/fetch_calib.hip): lower / upper bound
-                     "l1l2_amplification": (round(traffic["l2_requests_per_step"] * 64 / alg_bytes, 3)
-                                            if traffic and traffic.get("l2_requests_per_step") else None),
-                     "l1l2_amplification_128B": (round(traffic["l2_requests_per_step"] * 128 / alg_bytes, 3)
-                                                 if traffic and traffic.get("l2_requests_per_step") else None),
-                     "kernel": "mp2vg::recon_kernel", "launches_per_step": len(kernel_ms[0]),
-                     "avg_launch_ms": round(float(np.mean(per_launch)), 4),
-                     "algorithmic_bytes_per_step": int(alg_bytes), "bytes_breakdown": parts,
-                     "kernel_ms_per_step": round(kernel_step_ms, 4),
-                     "batch_span_ms": round(float(np.mean(batch_ms)), 4),
-                     "sum_launch_ms_per_step": round(float(np.mean([sum(s) for s in kernel_ms])), 4),
-                     "dominant_kernel": dominant, "one_stream_span_ms": round(span1, 4),
-                     "per_kernel": per_kernel},
-        "box": {"shader_clock_ghz_valu_load": clock_ghz, "host_cpus_visible": os.cpu_count()},
-        "pool_placement": {"candidate_batch_ms": place_ms, "kept": place_kept,
-                           "note": "runtime.cpp calibrate_placement, at the first warm-up batch: the batch "
-                                   "decoded on the pool and on copies in fresh blocks (round 0 of each, then "
-                                   "round 1), the fastest pool kept; outside the timed region"},
-        "frame_digest_of_digests": int(np.bitwise_xor.reduce(np.concatenate(gathered))),
-        "provenance": _build.provenance(),
-    }
-    if gather_res is not None:
-        result["frame_gather"] = gather_res
-    ctx.close()
-    if rank == 0 and world == 1 and dist is None and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(es, width, height, cf, parsed.npics)
-    if rank == 0 and world == 1 and dist is None and not args.no_e2e:
-        result["e2e_dropin"] = e2e_dropin(es, width, height, cf, parsed.npics, device,
-                                          result.get("cpu_baseline"))
-        result["e2e_dropin_device_frames"] = e2e_dropin(es, width, height, cf, parsed.npics, device,
-                                                        result.get("cpu_baseline"), device_frames=True)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
-    if parity["status"] == "MISMATCH":
-        sys.exit(3)
+    return {"parity": parity, "frame_gather": gather_res, "clock_ghz": clock_ghz,
+            "frame_digest_of_digests": int(np.bitwise_xor.reduce(np.concatenate(gathered))),
+            "roofline": {"dominant_kernel": dominant, "one_stream_span_ms": round(span1, 4), "per_kernel": per_kernel}}
 
 
 def e2e_dropin(es, width, height, cf, frames, device, cpu, device_frames=False):

@@ -27,7 +27,7 @@ def _free_port():
 def test_bench_two_ranks_gloo_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--gather-gops", "2"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--gather-gops", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -45,7 +45,7 @@ def test_bench_plain_gpus_2_spawns_its_ranks_on_one_gpu():
     ranks itself (one torch.distributed.run child) and the line reports n_gpus 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--gops", "4", "--gather-gops", "1"]
+           "--backend", "gloo", "--gops", "4", "--gather-gops", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -61,7 +61,7 @@ def test_bench_eight_ranks_c4_gloo_on_one_gpu():
     rank 0 gathers the first GOP of every rank in display order and checks it frame by frame."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--config", "c4", "--gops", "1",
-           "--steps", "2", "--warmup", "1", "--backend", "gloo", "--gather-gops", "1"]
+           "--steps", "2", "--warmup", "1", "--backend", "gloo", "--gather-gops", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -79,7 +79,7 @@ def test_bench_one_rank_over_rccl():
     collective of the 8-GPU scaling run, on the one MI355X a test box has."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "nccl", "--gather-gops", "2"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "nccl", "--gather-gops", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

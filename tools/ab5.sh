@@ -12,7 +12,7 @@ for r in $(seq 1 $R); do
     v=${arm%%@*}; envs=""; [ "$arm" != "$v" ] && envs=${arm#*@}
     if [ $v = base ]; then L=""; else L=tiny_mp2v_dec_amd/_var/$v/libmp2vg.so; fi
     tag=$(echo "$arm" | tr '=@,' '___')
-    env MP2VG_LIB=$L ${envs//,/ } timeout -k 10 240 python bench.py --no-cpu-baseline --no-e2e --config $CFG ${BENCH_ARGS:-} \
+    env MP2VG_LIB=$L ${envs//,/ } timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-e2e --config $CFG ${BENCH_ARGS:-} \
       > gpurun_out/ab5/${CFG}_$tag.$r.json 2> gpurun_out/ab5/${CFG}_$tag.$r.err
     rc=$?
     if [ $rc != 0 ] && [ $rc != 3 ]; then echo "$arm rc=$rc"; tail -3 gpurun_out/ab5/${CFG}_$tag.$r.err; exit 1; fi

@@ -36,7 +36,7 @@ def main():
     ap.add_argument("--json", help="write HBM traffic per bench step (bytes) for bench.py's roofline.traffic")
     ap.add_argument("--steps-total", type=int, default=18,
                     help="batches the profiled bench run decodes: steps + warmup + the 6 batches of its one-stream "
-                         "per-kernel context (bench.py: 10 + 2 + 6 by default)")
+                         "per-kernel context (bench.py --full, as tools/profile.sh runs it: 10 + 2 + 6 by default)")
     ap.add_argument("--config", default="c2")
     ap.add_argument("--gops", type=int, default=64)
     args = ap.parse_args()

@@ -12,7 +12,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 run() {  # name, rocprof args...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 "$@" --output-format csv -d $OUT/$name -o $name -- python3 bench.py --no-cpu-baseline $ARGS > $OUT/$name.log 2>&1
+  timeout -k 10 300 rocprofv3 "$@" --output-format csv -d $OUT/$name -o $name -- python3 bench.py --full --no-cpu-baseline $ARGS > $OUT/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc"
   return $rc

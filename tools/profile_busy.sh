@@ -6,6 +6,6 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 60 rocprofv3 -L > $OUT/avail.txt 2>&1 || true
 for m in VALUBusy VALUUtilization SALUBusy LDSBankConflict MemUnitBusy; do
-  timeout -k 10 150 rocprofv3 --kernel-trace --pmc $m --output-format csv -d $OUT/$m -o $m -- python3 bench.py --no-cpu-baseline "$@" > $OUT/$m.log 2>&1
+  timeout -k 10 150 rocprofv3 --kernel-trace --pmc $m --output-format csv -d $OUT/$m -o $m -- python3 bench.py --full --no-cpu-baseline "$@" > $OUT/$m.log 2>&1
   echo "$m rc=$?"
 done
