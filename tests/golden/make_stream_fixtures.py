@@ -55,6 +55,11 @@ CASES = [
                                               seed=1743)),
     ("ipb420_dense_i", 176, 144, 1, dict(n_gops=2, gop_n=6, gop_m=3, intra_coefs_min=20, intra_coefs_max=40,
                                           alternate_scan=-1, seed=1744)),
+    # row widths no other stream has: 45 MBs (720 px, remainder 1 mod the kernel's 4-MB group),
+    # 5 MBs (one full group and a one-MB group) and 3 MBs (narrower than one group)
+    ("sd480_420_field", 720, 480, 1, dict(n_gops=1, gop_n=6, gop_m=3, frame_pred_frame_dct=0, seed=1745)),
+    ("w80_422_field", 80, 48, 2, dict(n_gops=1, gop_n=12, gop_m=3, frame_pred_frame_dct=0, seed=1746)),
+    ("w48_444", 48, 32, 3, dict(n_gops=1, gop_n=12, gop_m=3, seed=1747)),
 ]
 
 
