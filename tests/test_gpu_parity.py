@@ -395,7 +395,8 @@ def test_reference_idct_vectors_through_hip():
     golden input exactly.  Picture 0 (I) puts the put-vectors; picture 1 (P, zero MV from
     picture 0) adds the add-vectors onto them, so the golden add output is the reference's add
     over the reference's own put output.  Hundreds of the blocks saturate int16 inside the
-    transform (put_saturates), so the kernel's saturating arithmetic is what is checked."""
+    transform (put_saturates), so the kernel's saturating arithmetic is what is checked.  Mismatch
+    control itself is checked in tests/test_gpu_dequant.py, on blocks whose toggle changes bytes."""
     import os
     from conftest import GOLDEN
     vec = np.load(os.path.join(GOLDEN, "idct_vectors.npz"))
