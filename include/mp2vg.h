@@ -240,6 +240,66 @@ int  mp2vg_pool_probe(mp2vg_ctx_t* ctx, int32_t rw, int32_t reps, double* gbps, 
  * (numpy twin: tiny_mp2v_dec_amd.records.planes_digest) */
 int  mp2vg_slot_digests(mp2vg_ctx_t* ctx, const int32_t* slots, int32_t n, uint64_t* out);
 
+/* ---- RGB export --------------------------------------------------------------------------
+ * Decoded frames (strided planar Y'CbCr in HBM) to tight uint8 R'G'B' tensors in HBM, cropped to
+ * a top-left anchored rectangle, one kernel launch per call (export.hip).  The reference stops at
+ * frame_c; this is what a consumer on a card without a display does next.
+ *
+ * The arithmetic is bit-exact, signed 32-bit, >> an arithmetic shift, results clamped to 0..255.
+ * Input is limited range (MPEG-2 always is), output full range:
+ *     yt = cy (Y - 16) + 8192
+ *     R = (yt + crv (Cr - 128)) >> 14
+ *     G = (yt + cgu (Cb - 128) + cgv (Cr - 128)) >> 14
+ *     B = (yt + cbu (Cb - 128)) >> 14
+ * with the 14-bit coefficients of mp2vg_export_coefficients.  Cb and Cr at luma (x, y) are 8-bit
+ * values, with MPEG-2 progressive siting (horizontally co-sited with even luma samples; 4:2:0:
+ * vertically midway between two luma rows):
+ *     NEAREST: C[4:2:0 ? y >> 1 : y][4:4:4 ? x : x >> 1]
+ *     LINEAR:  (wv0 (C[j][k] + C[j][k1]) + wv1 (C[j1][k] + C[j1][k1]) + 4) >> 3, one rounding;
+ *              4:2:0: j = y >> 1, j1 = j - 1 (y even) or j + 1 (y odd), wv0, wv1 = 3, 1; else
+ *              j1 = j = y, wv0, wv1 = 4, 0;  4:2:0 / 4:2:2: k = x >> 1, k1 = k (x even) or k + 1
+ *              (x odd); 4:4:4: k1 = k = x.  j1 and k1 clamp to the coded chroma plane, not to the
+ *              exported rectangle: a crop filters with the real neighbouring samples.
+ * Interlaced (field) chroma siting is out of scope: field pictures' chroma is filtered as if the
+ * frame were progressive. */
+enum { MP2VG_EXPORT_RGB_PLANAR = 0 /* [n][3][h][w] */, MP2VG_EXPORT_RGB_PACKED = 1 /* [n][h][w][3] */ };
+enum { MP2VG_EXPORT_CHROMA_NEAREST = 0, MP2VG_EXPORT_CHROMA_LINEAR = 1 };
+typedef struct mp2vg_export {
+    int32_t layout, matrix, chroma; /* MP2VG_EXPORT_RGB_*, matrix_coefficients code, MP2VG_EXPORT_CHROMA_* */
+    int32_t width, height;   /* exported rectangle, top-left anchored, 1..coded; 0 = coded size */
+    int32_t reserved[3];     /* must be 0 */
+} mp2vg_export_t;
+
+/* The fixed-point coefficients (cy, crv, cgu, cgv, cbu) of a matrix_coefficients code (ISO/IEC
+ * 13818-2 Table 6-9): 1 BT.709, 4 FCC, 5 / 6 BT.470BG / SMPTE 170M, 7 SMPTE 240M; any other code
+ * is MP2VG_E_INVALID.  Each is floor(x 2^14 + 1/2) of the exact rational, Kg = 1 - Kr - Kb:
+ * cy = 255/219, crv = (255/224) 2 (1 - Kr), cbu = (255/224) 2 (1 - Kb),
+ * cgu = -round((255/224) 2 (1 - Kb) Kb / Kg), cgv = -round((255/224) 2 (1 - Kr) Kr / Kg).
+ * Host only; the kernel's constants come from this table. */
+int  mp2vg_export_coefficients(int32_t matrix, int32_t out[5]);
+/* (mp2vg_export_matrix, below the stream headers: the matrix code to export a stream with) */
+/* bytes of the tensor n exported frames fill (n 3 w h), after validating the export against the
+ * geometry of cfg; no device needed */
+int  mp2vg_export_bytes(const mp2vg_config_t* cfg, const mp2vg_export_t* exp, int32_t n, uint64_t* bytes);
+/* Export frame i from slot slots[i] (any order, repeats allowed: display order is a slot list; n
+ * at most 65535) into the tight tensor at dst_device (any byte alignment; dst_bytes must equal
+ * mp2vg_export_bytes), all n frames in one launch.  Asynchronous: enqueued on the context's main
+ * stream behind every decode enqueued so far, complete after mp2vg_synchronize; a later
+ * mp2vg_batch_decode waits for it before it overwrites a slot.  The slot list is copied before
+ * the call returns.  The main stream is not ordered with streams of the caller's: other work on
+ * dst must have finished before the call, and other streams read dst after mp2vg_synchronize.
+ * Every argument is checked before the first HIP call. */
+int  mp2vg_export_slots(mp2vg_ctx_t* ctx, const int32_t* slots, int32_t n, const mp2vg_export_t* exp,
+                        void* dst_device, uint64_t dst_bytes);
+/* The same kernel over one frame at arbitrary device plane pointers (a device frame inside the
+ * render callback of an MP2VG_DECODER_DEVICE_FRAMES decoder, or a caller's own planes) of a
+ * coded_w x coded_h frame: planes 4-byte aligned, strides multiples of 4 and at least the plane's
+ * width (else MP2VG_E_INVALID), each plane readable over stride x plane height bytes.
+ * Synchronous (a callback frame dies on return). */
+int  mp2vg_export_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                         int32_t chroma_format, int32_t coded_w, int32_t coded_h, const mp2vg_export_t* exp,
+                         void* dst_device, uint64_t dst_bytes);
+
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c
  * (decoder.h:124-130), with the reference's field names (mp2v_hdr.h:61-141) and parsed the way
@@ -282,6 +342,12 @@ typedef struct mp2vg_stream_headers {
     mp2vg_sequence_display_extension_t sequence_display_extension;
     mp2vg_group_of_pictures_header_t group_of_pictures_header; /* the last one in the stream      */
 } mp2vg_stream_headers_t;
+
+/* The matrix code to export a stream with (RGB export, above): its matrix_coefficients when the
+ * sequence display extension carries a colour description and the code is 1, 4, 5, 6 or 7; 1
+ * (BT.709, the assumption of 13818-2 6.3.6) when the extension or the description is absent or
+ * the code is 2 ("unspecified"); MP2VG_E_UNSUPPORTED for 0, 3 and codes above 7. */
+int  mp2vg_export_matrix(const mp2vg_stream_headers_t* headers, int32_t* matrix);
 
 /* ---- host record emitter -------------------------------------------------------------- */
 typedef struct mp2vg_parsed mp2vg_parsed_t;

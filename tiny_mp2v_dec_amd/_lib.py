@@ -103,6 +103,14 @@ class StreamHeaders(ctypes.Structure):  # mp2vg_stream_headers_t
                 ("group_of_pictures_header", GopHeader)]
 
 
+class Export(ctypes.Structure):  # mp2vg_export_t
+    _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("chroma", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+EXPORT_RGB_PLANAR, EXPORT_RGB_PACKED = 0, 1
+EXPORT_CHROMA_NEAREST, EXPORT_CHROMA_LINEAR = 0, 1
+
 RENDER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(Frame))
 
 # every symbol declared in include/mp2vg.h
@@ -117,6 +125,8 @@ EXPORTS = [
     "mp2vg_decoder_create_multi", "mp2vg_decoder_decode", "mp2vg_decoder_stream_headers",
     "mp2vg_decoder_lane_frames", "mp2vg_decoder_frames_allocated", "mp2vg_decoder_handoff_stats",
     "mp2vg_decoder_destroy",
+    "mp2vg_export_coefficients", "mp2vg_export_matrix", "mp2vg_export_bytes", "mp2vg_export_slots",
+    "mp2vg_export_planes",
 ]
 
 _lib = None
@@ -180,6 +190,11 @@ def lib():
         "mp2vg_decoder_frames_allocated": ([VP], ctypes.c_int),
         "mp2vg_decoder_handoff_stats": ([VP, P(I32), P(I32), P(I32), P(I32)], ctypes.c_int),
         "mp2vg_decoder_destroy": ([VP], ctypes.c_int),
+        "mp2vg_export_coefficients": ([I32, P(I32)], ctypes.c_int),
+        "mp2vg_export_matrix": ([P(StreamHeaders), P(I32)], ctypes.c_int),
+        "mp2vg_export_bytes": ([P(Config), P(Export), I32, P(U64)], ctypes.c_int),
+        "mp2vg_export_slots": ([VP, P(I32), I32, P(Export), VP, U64], ctypes.c_int),
+        "mp2vg_export_planes": ([I32, P(VP), P(I32), I32, I32, I32, P(Export), VP, U64], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -201,6 +216,40 @@ MP2VG_DECODER_DEVICE_FRAMES, MP2VG_CTX_ONE_STREAM = 1, 2  # mp2vg_config_t.reser
 
 def make_config(width, height, chroma_format, pool=10, threads=0, reordering=True, device=0, flags=0):
     return Config(width, height, chroma_format, pool, threads, 1 if reordering else 0, device, flags)
+
+
+def make_export(layout="nchw", chroma="linear", matrix=1, size=None):
+    """mp2vg_export_t from the Python spelling: layout "nchw" (planar) / "nhwc" (packed), chroma
+    "linear" / "nearest", matrix = a matrix_coefficients code, size = (width, height) or None for
+    the coded size."""
+    layouts = {"nchw": EXPORT_RGB_PLANAR, "nhwc": EXPORT_RGB_PACKED}
+    modes = {"nearest": EXPORT_CHROMA_NEAREST, "linear": EXPORT_CHROMA_LINEAR}
+    if layout not in layouts:
+        raise ValueError(f"layout {layout!r}: expected 'nchw' or 'nhwc'")
+    if chroma not in modes:
+        raise ValueError(f"chroma {chroma!r}: expected 'linear' or 'nearest'")
+    w, h = (0, 0) if size is None else (int(size[0]), int(size[1]))
+    return Export(layouts[layout], int(matrix), modes[chroma], w, h, (ctypes.c_int32 * 3)())
+
+
+def export_shape(exp, n, coded_w, coded_h):
+    """Tensor shape of n frames exported with `exp` from coded_w x coded_h frames."""
+    w, h = exp.width or coded_w, exp.height or coded_h
+    return (n, 3, h, w) if exp.layout == EXPORT_RGB_PLANAR else (n, h, w, 3)
+
+
+def export_out(out, shape, device):
+    """The tensor an export writes: `out` after checking device, dtype, shape and contiguity, or
+    a new torch.uint8 tensor on cuda:<device>.  torch is imported here, not with the package."""
+    import torch
+    dev = torch.device("cuda", device)
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=dev)
+    if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8:
+        raise ValueError(f"out must be a torch.uint8 tensor on {dev}")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous with shape {tuple(shape)}, got {tuple(out.shape)}")
+    return out
 
 
 def geometry(width, height, chroma_format):

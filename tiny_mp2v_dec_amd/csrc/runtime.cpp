@@ -15,6 +15,8 @@
 #include <atomic>
 #include <thread>
 
+#include "export_kernel.h"
+#include "hipchk.h"
 #include "recon_kernel.h"
 #include "syntax.h"
 
@@ -33,14 +35,6 @@ hipError_t launch_digest(const uint64_t* ftab, const int32_t* d_slots, int n,
 
 using namespace mp2vg;
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-            return MP2VG_E_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
 
 static constexpr size_t kPoolPad = 4096 + 65536;  // slack after the last slot: clamped row over-reads, the
                                                   // kernel's dummy load / store sink at +2048 (kSinkOff) and,
@@ -187,6 +181,26 @@ struct mp2vg_ctx {
     int32_t* d_dslots = nullptr;
     unsigned long long* d_digest = nullptr;
     size_t cap_digest = 0;
+
+    // mp2vg_export_slots: slot lists in flight (pinned host copy -> device copy on the main stream,
+    // a ring so that back-to-back exports do not wait for each other) and the event the next
+    // batch's set streams wait on before they overwrite slots an export still reads
+    struct ExportStage {
+        int32_t* h = nullptr;
+        int32_t* d = nullptr;
+        size_t cap = 0;
+        hipEvent_t done = nullptr;  // after the export kernel that read d
+    };
+    static constexpr int kExportRing = 4;
+    ExportStage estage[kExportRing];
+    uint32_t eseq = 0;               // exports enqueued
+    hipEvent_t export_ev = nullptr;  // after the last export (main stream)
+    // Per set stream: the export count it has waited for.  A batch uses only as many set streams as
+    // it has picture sets, so each stream waits on export_ev the first time it is used after an
+    // export, whichever batch that is; a stream created later starts at export_synced, the count
+    // when the main stream was last synchronised.  Callers that never export never wait.
+    std::vector<uint32_t> swaited;
+    uint32_t export_synced = 0;
 };
 
 template <class T>
@@ -316,6 +330,12 @@ extern "C" int mp2vg_destroy(mp2vg_ctx_t* c) {
     }
     hipFree(c->d_dslots);
     hipFree(c->d_digest);
+    for (auto& e : c->estage) {
+        if (e.h) hipHostFree(e.h);
+        hipFree(e.d);
+        if (e.done) hipEventDestroy(e.done);
+    }
+    if (c->export_ev) hipEventDestroy(c->export_ev);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (auto st : c->sstreams) hipStreamSynchronize(st);
     for (auto e : c->sev) hipEventDestroy(e);
@@ -1268,6 +1288,7 @@ static int batch_decode(mp2vg_ctx_t* c) {
         HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->sstreams.push_back(st);
         c->sev.push_back(e);
+        c->swaited.push_back(c->export_synced);
     }
     auto stream_of = [&](int set) { return c->sstreams[set]; };
     for (int set = 0; set < nsets; set++) {
@@ -1277,6 +1298,11 @@ static int batch_decode(mp2vg_ctx_t* c) {
             bool overlap = set >= (int)b.foot.size();  // no footprint: wait for everything
             for (size_t i = 0; !overlap && i < b.foot[set].size(); i++) overlap = c->last_foot[t][b.foot[set][i]];
             if (overlap) HIPCHK(hipStreamWaitEvent(st, c->sev[t], 0));
+        }
+        // exports enqueued on the main stream since this stream last waited may still read slots
+        if (c->swaited[set] != c->eseq) {
+            HIPCHK(hipStreamWaitEvent(st, c->export_ev, 0));
+            c->swaited[set] = c->eseq;
         }
     }
     // stale anchor tiles of slots this batch reads from earlier batches (rare: an MPEG-2 stream's
@@ -1358,6 +1384,8 @@ extern "C" int mp2vg_synchronize(mp2vg_ctx_t* c) {
     if (!c) return MP2VG_E_INVALID;
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->export_synced = c->eseq;  // every export has completed
+    std::fill(c->swaited.begin(), c->swaited.end(), c->eseq);
     return MP2VG_OK;
 }
 
@@ -1607,3 +1635,123 @@ extern "C" int mp2vg_slot_digests(mp2vg_ctx_t* c, const int32_t* slots, int32_t 
     HIPCHK(hipStreamSynchronize(c->stream));
     return MP2VG_OK;
 }
+
+// ---- RGB export (include/mp2vg.h "RGB export"; kernel: export.hip) ---------------------------
+
+// Kr, Kb of a matrix_coefficients code as num / den (ISO/IEC 13818-2 Table 6-9)
+static bool matrix_primaries(int32_t matrix, int64_t* nr, int64_t* nb, int64_t* den) {
+    switch (matrix) {
+        case 1: *nr = 2126, *nb = 722, *den = 10000; return true;  // BT.709
+        case 4: *nr = 30, *nb = 11, *den = 100; return true;       // FCC
+        case 5:
+        case 6: *nr = 299, *nb = 114, *den = 1000; return true;    // BT.470BG / SMPTE 170M
+        case 7: *nr = 212, *nb = 87, *den = 1000; return true;     // SMPTE 240M
+    }
+    return false;
+}
+
+// floor(num / den * 2^14 + 1/2) for a positive rational
+static int32_t q14(int64_t num, int64_t den) { return (int32_t)((num * 32768 + den) / (2 * den)); }
+
+extern "C" int mp2vg_export_coefficients(int32_t matrix, int32_t out[5]) {
+    int64_t nr, nb, d;
+    if (!out || !matrix_primaries(matrix, &nr, &nb, &d)) return MP2VG_E_INVALID;
+    const int64_t ng = d - nr - nb;
+    out[0] = q14(255, 219);                                      // cy
+    out[1] = q14(510 * (d - nr), 224 * d);                       // crv
+    out[2] = -q14(510 * (d - nb) * nb, 224 * d * ng);            // cgu
+    out[3] = -q14(510 * (d - nr) * nr, 224 * d * ng);            // cgv
+    out[4] = q14(510 * (d - nb), 224 * d);                       // cbu
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_export_matrix(const mp2vg_stream_headers_t* h, int32_t* matrix) {
+    if (!h || !matrix) return MP2VG_E_INVALID;
+    *matrix = 1;
+    if (!h->have_sequence_display_extension || !h->sequence_display_extension.colour_description) return MP2VG_OK;
+    const uint32_t m = h->sequence_display_extension.matrix_coefficients;
+    if (m == 2) return MP2VG_OK;  // "unspecified"
+    if (m == 1 || (m >= 4 && m <= 7)) {
+        *matrix = (int32_t)m;
+        return MP2VG_OK;
+    }
+    set_error("matrix_coefficients " + std::to_string(m) + " has no RGB export matrix");
+    return MP2VG_E_UNSUPPORTED;
+}
+
+// checks an export against a coded size; the exported rectangle in *w, *h
+namespace mp2vg {
+int check_export(const mp2vg_export_t* e, int32_t coded_w, int32_t coded_h, int32_t* w, int32_t* h) {
+    int32_t k[5];
+    if (!e) return MP2VG_E_INVALID;
+    const char* why = nullptr;
+    if (e->layout != MP2VG_EXPORT_RGB_PLANAR && e->layout != MP2VG_EXPORT_RGB_PACKED) why = "layout";
+    else if (e->chroma != MP2VG_EXPORT_CHROMA_NEAREST && e->chroma != MP2VG_EXPORT_CHROMA_LINEAR) why = "chroma mode";
+    else if (mp2vg_export_coefficients(e->matrix, k) != MP2VG_OK) why = "matrix code";
+    else if (e->reserved[0] || e->reserved[1] || e->reserved[2]) why = "reserved fields";
+    else if (e->width < 0 || e->width > coded_w || e->height < 0 || e->height > coded_h) why = "rectangle";
+    if (why) {
+        set_error(std::string("export: bad ") + why);
+        return MP2VG_E_INVALID;
+    }
+    *w = e->width ? e->width : coded_w;
+    *h = e->height ? e->height : coded_h;
+    return MP2VG_OK;
+}
+}  // namespace mp2vg
+
+extern "C" int mp2vg_export_bytes(const mp2vg_config_t* cfg, const mp2vg_export_t* e, int32_t n, uint64_t* bytes) {
+    if (!cfg || !bytes || n <= 0 || mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK)
+        return MP2VG_E_INVALID;
+    int32_t w, h;
+    if (int rc = check_export(e, cfg->width, cfg->height, &w, &h)) return rc;
+    *bytes = (uint64_t)n * 3 * (uint64_t)w * (uint64_t)h;
+    return MP2VG_OK;
+}
+
+// What mp2vg_export_slots (export.cpp) needs from a context: its geometry and slot table, a device
+// copy of the slot list (ring of pinned + device buffers on the main stream, so back-to-back
+// exports do not wait for each other), and the bookkeeping after the kernel is enqueued.
+namespace mp2vg {
+void export_source(const mp2vg_ctx* c, ExportSource* s) {
+    s->device = c->cfg.device;
+    s->cf = c->g.cf;
+    s->nslots = c->nslots;
+    s->pw = c->g.pw[0], s->ph = c->g.ph[0], s->cw = c->g.pw[1], s->ch = c->g.ph[1];
+    for (int p = 0; p < 3; p++) {
+        s->stride[p] = c->g.stride[p];
+        s->plane_off[p] = (uint32_t)c->g.plane_off[p];
+    }
+    s->ftab = c->d_tab;
+    s->stream = c->stream;
+}
+
+int export_stage_slots(mp2vg_ctx* c, const int32_t* slots, int32_t n, const int32_t** d_slots) {
+    mp2vg_ctx::ExportStage& st = c->estage[c->eseq % mp2vg_ctx::kExportRing];
+    if (!st.done) HIPCHK(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    HIPCHK(hipEventSynchronize(st.done));  // the export that last used this list has read it
+    if ((size_t)n > st.cap) {
+        if (st.h) HIPCHK(hipHostFree(st.h));
+        if (st.d) HIPCHK(hipFree(st.d));
+        st.h = st.d = nullptr;
+        st.cap = 0;
+        const size_t cap = std::max<size_t>(n, 256);
+        HIPCHK(hipHostMalloc((void**)&st.h, cap * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void**)&st.d, cap * sizeof(int32_t)));
+        st.cap = cap;
+    }
+    if (!c->export_ev) HIPCHK(hipEventCreateWithFlags(&c->export_ev, hipEventDisableTiming));
+    memcpy(st.h, slots, sizeof(int32_t) * n);
+    HIPCHK(hipMemcpyAsync(st.d, st.h, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    *d_slots = st.d;
+    return MP2VG_OK;
+}
+
+int export_enqueued(mp2vg_ctx* c) {
+    mp2vg_ctx::ExportStage& st = c->estage[c->eseq % mp2vg_ctx::kExportRing];
+    HIPCHK(hipEventRecord(st.done, c->stream));
+    HIPCHK(hipEventRecord(c->export_ev, c->stream));
+    c->eseq++;
+    return MP2VG_OK;
+}
+}  // namespace mp2vg

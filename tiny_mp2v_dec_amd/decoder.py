@@ -89,6 +89,22 @@ class frame_c:  # noqa: N801  (reference name)
             raise ValueError("host frame: use get_planes")
         return ctypes.cast(self._f.planes[i], ctypes.c_void_p).value
 
+    def export_rgb(self, out=None, layout="nchw", chroma="linear", matrix=1, size=None):
+        """This frame as a torch.uint8 RGB tensor on its device, (1, 3, h, w) for layout "nchw" or
+        (1, h, w, 3) for "nhwc" (mp2vg_export_planes; arguments as DeviceContext.export_rgb).
+        Device frames only (decoder_config_t(device_frames=True)); complete on return, so the
+        tensor outlives the callback."""
+        if not self.is_device:
+            raise ValueError("host frame: export_rgb needs a device_frames=True decoder")
+        f = self._f
+        cf = 3 if f.width[1] == f.width[0] else (2 if f.height[1] == f.height[0] else 1)
+        exp = _lib.make_export(layout, chroma, matrix, size)
+        t = _lib.export_out(out, _lib.export_shape(exp, 1, f.width[0], f.height[0]), f.device)
+        planes = (ctypes.c_void_p * 3)(*[self.device_ptr(i) for i in range(3)])
+        check(lib().mp2vg_export_planes(f.device, planes, f.stride, cf, f.width[0], f.height[0], ctypes.byref(exp),
+                                        ctypes.c_void_p(t.data_ptr()), t.numel()), "export_planes")
+        return t
+
     def get_strides(self, i):
         return self._f.stride[i]
 

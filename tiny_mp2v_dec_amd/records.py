@@ -224,11 +224,75 @@ class DeviceContext:
         check(lib().mp2vg_copy_slot_packed(self.h, int(slot), ctypes.c_void_p(dst_ptr), 1 if on_device else 0),
               "copy_slot_packed")
 
+    def export_rgb(self, slots, out=None, layout="nchw", chroma="linear", matrix=1, size=None, sync=True):
+        """Frames of `slots` (any order, repeats allowed) as one torch.uint8 RGB tensor on this
+        context's device (mp2vg_export_slots: one kernel launch, no PCIe): (n, 3, h, w) for layout
+        "nchw", (n, h, w, 3) for "nhwc"; chroma "linear" / "nearest" upsampling; matrix = a
+        matrix_coefficients code (1 BT.709, 4 FCC, 5 / 6 BT.601, 7 SMPTE 240M); size = (width,
+        height) of the top-left rectangle exported (None: the coded size).  Writes into `out` when
+        given.  The export is enqueued behind the decodes enqueued so far; with sync=False it is
+        complete only after synchronize().
+
+        The export runs on the context's own (non-blocking) stream, which is not ordered with
+        torch's streams: work torch has enqueued on `out` (a fill, or the last kernels that used a
+        block the caching allocator hands back) must have finished before the call
+        (torch.cuda.synchronize() or a stream synchronise; the producer side is the caller's job),
+        and with sync=False torch must not read the tensor before synchronize().  At most 65535
+        slots per call."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        exp = _lib.make_export(layout, chroma, matrix, size)
+        shape = _lib.export_shape(exp, len(slots), self.width, self.height)
+        t = _lib.export_out(out, shape, self.cfg.device)
+        check(lib().mp2vg_export_slots(self.h, slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(slots),
+                                       ctypes.byref(exp), ctypes.c_void_p(t.data_ptr()), t.numel()), "export_slots")
+        if sync:
+            self.synchronize()
+        return t
+
     def digests(self, slots):
         slots = np.ascontiguousarray(slots, np.int32)
         out = np.zeros(len(slots), np.uint64)
         check(lib().mp2vg_slot_digests(self.h, slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(slots),
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))), "slot_digests")
+        return out
+
+
+EXPORT_MAX_FRAMES = 65535  # frames per mp2vg_export_slots call (include/mp2vg.h)
+
+
+def export_matrix(headers):
+    """The matrix_coefficients code to export a stream with (mp2vg_export_matrix): the stream's own
+    when it carries a usable one, else 1 (BT.709)."""
+    m = ctypes.c_int32()
+    check(lib().mp2vg_export_matrix(ctypes.byref(headers), ctypes.byref(m)), "export_matrix")
+    return m.value
+
+
+def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0):
+    """Decode a whole elementary stream (coded size width x height) and return its pictures in
+    display order as one torch.uint8 RGB tensor on cuda:<device>, cropped to the sequence header's
+    horizontal_size_value x vertical_size_value when these are set and no larger than the coded
+    size.  matrix=None takes the stream's matrix_coefficients (export_matrix).  The stream is one
+    batch in a context of as many slots as it has pictures; a stream without pictures gives an
+    empty tensor, and one of more than 65535 pictures is exported in several calls."""
+    parsed = Parsed(es, width, height, chroma_format)
+    sh = parsed.headers.sequence_header
+    w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
+    size = (w, h) if 0 < w <= width and 0 < h <= height else None
+    if matrix is None:
+        matrix = export_matrix(parsed.headers)
+    exp = _lib.make_export(layout, chroma, matrix, size)
+    out = _lib.export_out(None, _lib.export_shape(exp, parsed.npics, width, height), device)
+    if not parsed.npics:
+        return out
+    with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
+        ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        ctx.decode()
+        for i in range(0, parsed.npics, EXPORT_MAX_FRAMES):  # mp2vg_export_slots takes 65535 per call
+            part = parsed.display[i:i + EXPORT_MAX_FRAMES]
+            ctx.export_rgb(part, out=out[i:i + len(part)], layout=layout, chroma=chroma, matrix=matrix, size=size,
+                           sync=False)
+        ctx.synchronize()
         return out
 
 
