@@ -300,6 +300,79 @@ int  mp2vg_export_planes(int32_t device, const uint8_t* const planes[3], const i
                          int32_t chroma_format, int32_t coded_w, int32_t coded_h, const mp2vg_export_t* exp,
                          void* dst_device, uint64_t dst_bytes);
 
+/* ---- tensor export -----------------------------------------------------------------------
+ * Decoded frames to cropped, antialias-resized, normalised model-input tensors in HBM, one kernel
+ * launch per call (tensor.hip): Y'CbCr -> R'G'B', crop, both filter passes, normalise and cast in
+ * one pass over the planes, with no full-size RGB intermediate in memory.  The result is defined
+ * to the bit, by composition on top of the RGB export:
+ *
+ * 1. Source image.  The 8-bit R'G'B' image P of the WHOLE coded frame exactly as the RGB export
+ *    above defines it (matrix, NEAREST or LINEAR chroma, chroma taps clamped to the coded chroma
+ *    plane), cropped to the rectangle (src_x, src_y, src_w, src_h) in luma pixels: any integers
+ *    inside the coded frame, odd origins included.  src_w = src_h = 0 (with src_x = src_y = 0)
+ *    is the whole coded frame.
+ * 2. Tap table of one axis (src source pixels of the rectangle, out output pixels): the triangle
+ *    ("antialiased bilinear") filter with half-pixel centres, in exact rationals:
+ *        r = src / out, s = max(r, 1), c(o) = (o + 1/2) r
+ *        first = max(0, floor(c - s + 1/2)), end = min(src, floor(c + s + 1/2))
+ *        t_j = max(0, 1 - |j + 1/2 - c| / s)                    for j in [first, end)
+ *        q_j = floor(t_j / sum(t) 2^14 + 1/2), then 2^14 - sum(q) is added to the tap with the
+ *        largest t_j (the lowest j on a tie)
+ *    so the weights of an output are non-negative 14-bit integers that sum to exactly 16384.
+ *    Taps outside the rectangle do not exist: nothing beyond the crop is read (the chroma taps of
+ *    step 1 still reach the real neighbouring samples).  r <= 32 per axis (at most
+ *    MP2VG_TENSOR_MAX_TAPS = 65 taps), else MP2VG_E_INVALID; out > src (upscaling) is allowed;
+ *    out_w, out_h at most 16384.
+ * 3. Vertical pass, then horizontal pass, per channel, signed 32-bit, >> an arithmetic shift:
+ *        V[y][x] = (sum_j qv_j P[j][x] + 128) >> 8             6 fractional bits, 0..16320
+ *        Q[y][x] = (sum_k qh_k V[y][k] + 8192) >> 14           units of 1/64 of an 8-bit step
+ *    With out == src on both axes this is the identity, Q = 64 P.
+ * 4. Output element of channel c:
+ *        U8:   (Q + 32) >> 6; scale must be {1, 1, 1} and bias {0, 0, 0}
+ *        F32:  fmaf(Q / 64, scale[c], bias[c]): one rounding of the exact value (Q / 64 is exact)
+ *        F16 / BF16: that float32 value rounded to nearest even
+ *    scale and bias must be finite.  (x / 255 - mean) / std is scale = 1 / (255 std), bias =
+ *    -mean / std.
+ * 5. Layout: planar [n][3][out_h][out_w] or packed [n][out_h][out_w][3] (MP2VG_EXPORT_RGB_*),
+ *    tight; dst is aligned to the element size and no more.
+ * Out of scope: interlaced chroma siting (as above), filters other than the triangle, padding. */
+enum { MP2VG_TENSOR_U8 = 0, MP2VG_TENSOR_F16 = 1, MP2VG_TENSOR_BF16 = 2, MP2VG_TENSOR_F32 = 3 };
+#define MP2VG_TENSOR_MAX_TAPS 65
+typedef struct mp2vg_tensor {
+    int32_t layout, matrix, chroma; /* as mp2vg_export_t */
+    int32_t src_x, src_y, src_w, src_h; /* source rectangle, luma pixels; all 0 = the coded frame */
+    int32_t out_w, out_h;    /* 1..16384, each at least 1/32 of the rectangle's side */
+    int32_t dtype;           /* MP2VG_TENSOR_* */
+    float   scale[3], bias[3]; /* per channel R, G, B */
+    int32_t reserved[4];     /* must be 0 */
+} mp2vg_tensor_t;            /* 80 bytes */
+
+/* The tap table of one axis as the library computes it (integer arithmetic only; host only):
+ * output o takes taps first[o] .. first[o] + count[o] - 1 with weights[o * max_taps + k], entries
+ * from count[o] to max_taps zero.  first, count: out entries; weights: out * max_taps.
+ * MP2VG_E_INVALID when src < 1, out < 1, out > 16384, src > 32 out, or an output has more than
+ * max_taps taps (MP2VG_TENSOR_MAX_TAPS always suffices). */
+int  mp2vg_tensor_weights(int32_t src, int32_t out, int32_t* first, int32_t* count, int32_t* weights,
+                          int32_t max_taps);
+/* bytes of the tensor n frames fill (n 3 out_w out_h element size), after validating t against
+ * the geometry of cfg; no device needed */
+int  mp2vg_tensor_bytes(const mp2vg_config_t* cfg, const mp2vg_tensor_t* t, int32_t n, uint64_t* bytes);
+/* Frame i from slot slots[i] (any order, repeats allowed; n at most 65535) into the tight tensor
+ * at dst_device (aligned to the element size; dst_bytes must equal mp2vg_tensor_bytes), all n
+ * frames in one launch.  Ordering as mp2vg_export_slots, whose events it shares: asynchronous on
+ * the context's main stream behind every decode enqueued so far, complete after
+ * mp2vg_synchronize; a later mp2vg_batch_decode waits for it before it overwrites a slot.  The
+ * slot list and the two tap tables are copied before the call returns.  The main stream is not
+ * ordered with streams of the caller's (see mp2vg_export_slots).  Every argument is checked
+ * before the first HIP call. */
+int  mp2vg_tensor_slots(mp2vg_ctx_t* ctx, const int32_t* slots, int32_t n, const mp2vg_tensor_t* t,
+                        void* dst_device, uint64_t dst_bytes);
+/* The same kernel over one frame at arbitrary device plane pointers, with the plane
+ * preconditions of mp2vg_export_planes.  Synchronous. */
+int  mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                         int32_t chroma_format, int32_t coded_w, int32_t coded_h, const mp2vg_tensor_t* t,
+                         void* dst_device, uint64_t dst_bytes);
+
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c
  * (decoder.h:124-130), with the reference's field names (mp2v_hdr.h:61-141) and parsed the way

@@ -4,6 +4,6 @@ Host record emitter + HIP/CDNA4 kernels behind the C ABI of include/mp2vg.h, wit
 reference's decoder API (mp2v_decoder_c / frame_c / decoder_config_t) mirrored in decoder.py.
 """
 from ._lib import MB_DTYPE, PIC_DTYPE, Mp2vgError, lib  # noqa: F401
-from .records import DeviceContext, Parsed, decode_rgb, generate_es  # noqa: F401
+from .records import DeviceContext, Parsed, decode_rgb, decode_tensor, generate_es  # noqa: F401
 
-__all__ = ["DeviceContext", "Parsed", "decode_rgb", "generate_es", "MB_DTYPE", "PIC_DTYPE", "Mp2vgError", "lib"]
+__all__ = ["DeviceContext", "Parsed", "decode_rgb", "decode_tensor", "generate_es", "MB_DTYPE", "PIC_DTYPE", "Mp2vgError", "lib"]

@@ -111,6 +111,19 @@ class Export(ctypes.Structure):  # mp2vg_export_t
 EXPORT_RGB_PLANAR, EXPORT_RGB_PACKED = 0, 1
 EXPORT_CHROMA_NEAREST, EXPORT_CHROMA_LINEAR = 0, 1
 
+class Tensor(ctypes.Structure):  # mp2vg_tensor_t
+    _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("chroma", ctypes.c_int32),
+                ("src_x", ctypes.c_int32), ("src_y", ctypes.c_int32), ("src_w", ctypes.c_int32),
+                ("src_h", ctypes.c_int32), ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
+TENSOR_MAX_TAPS = 65
+TENSOR_DTYPES = {"uint8": (TENSOR_U8, 1), "float16": (TENSOR_F16, 2), "bfloat16": (TENSOR_BF16, 2),
+                 "float32": (TENSOR_F32, 4)}  # name -> (MP2VG_TENSOR_*, element size)
+
 RENDER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(Frame))
 
 # every symbol declared in include/mp2vg.h
@@ -127,6 +140,7 @@ EXPORTS = [
     "mp2vg_decoder_destroy",
     "mp2vg_export_coefficients", "mp2vg_export_matrix", "mp2vg_export_bytes", "mp2vg_export_slots",
     "mp2vg_export_planes",
+    "mp2vg_tensor_weights", "mp2vg_tensor_bytes", "mp2vg_tensor_slots", "mp2vg_tensor_planes",
 ]
 
 _lib = None
@@ -195,6 +209,10 @@ def lib():
         "mp2vg_export_bytes": ([P(Config), P(Export), I32, P(U64)], ctypes.c_int),
         "mp2vg_export_slots": ([VP, P(I32), I32, P(Export), VP, U64], ctypes.c_int),
         "mp2vg_export_planes": ([I32, P(VP), P(I32), I32, I32, I32, P(Export), VP, U64], ctypes.c_int),
+        "mp2vg_tensor_weights": ([I32, I32, P(I32), P(I32), P(I32), I32], ctypes.c_int),
+        "mp2vg_tensor_bytes": ([P(Config), P(Tensor), I32, P(U64)], ctypes.c_int),
+        "mp2vg_tensor_slots": ([VP, P(I32), I32, P(Tensor), VP, U64], ctypes.c_int),
+        "mp2vg_tensor_planes": ([I32, P(VP), P(I32), I32, I32, I32, P(Tensor), VP, U64], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -250,6 +268,68 @@ def export_out(out, shape, device):
     if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
         raise ValueError(f"out must be contiguous with shape {tuple(shape)}, got {tuple(out.shape)}")
     return out
+
+
+def tensor_dtype_name(dtype):
+    """"uint8" / "float16" / "bfloat16" / "float32" from that name or the torch dtype."""
+    name = str(dtype).replace("torch.", "")
+    if name not in TENSOR_DTYPES:
+        raise ValueError(f"dtype {dtype!r}: expected uint8, float16, bfloat16 or float32")
+    return name
+
+
+def make_tensor(size, crop=None, dtype="float16", mean=None, std=None, layout="nchw", chroma="linear", matrix=1):
+    """mp2vg_tensor_t from the Python spelling: size = (out_w, out_h); crop = (x, y, w, h) in luma
+    pixels or None for the coded frame; dtype a name or torch dtype; mean / std per channel in 0..1
+    units (both or neither): scale = float32(1 / (255 std)), bias = float32(-mean / std), computed
+    in float64 and rounded once; without them scale 1 / 255 and bias 0 (uint8: 1 and 0, and mean /
+    std are refused); layout, chroma, matrix as make_export."""
+    e = make_export(layout, chroma, matrix)
+    name = tensor_dtype_name(dtype)
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if name == "uint8":
+        if mean is not None:
+            raise ValueError("uint8 output takes no mean / std")
+        scale, bias = [1.0] * 3, [0.0] * 3
+    elif mean is None:
+        scale, bias = [1.0 / 255.0] * 3, [0.0] * 3
+    else:
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("mean and std have one entry per channel")
+        scale, bias = [1.0 / (255.0 * s) for s in std], [-m / s for m, s in zip(mean, std)]
+    x, y, w, h = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+    return Tensor(e.layout, e.matrix, e.chroma, x, y, w, h, int(size[0]), int(size[1]), TENSOR_DTYPES[name][0],
+                  (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias), (ctypes.c_int32 * 4)())
+
+
+def tensor_shape(t, n):
+    return (n, 3, t.out_h, t.out_w) if t.layout == EXPORT_RGB_PLANAR else (n, t.out_h, t.out_w, 3)
+
+
+def tensor_out(out, shape, dtype, device):
+    """The tensor a tensor export writes: `out` after checking device, dtype, shape and contiguity,
+    or a new tensor of that dtype on cuda:<device>."""
+    import torch
+    dev, want = torch.device("cuda", device), getattr(torch, tensor_dtype_name(dtype))
+    if out is None:
+        return torch.empty(shape, dtype=want, device=dev)
+    if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != want:
+        raise ValueError(f"out must be a {want} tensor on {dev}")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous with shape {tuple(shape)}, got {tuple(out.shape)}")
+    return out
+
+
+def tensor_weights(src, out):
+    """(first, count, weights[out][max count]) of one axis (mp2vg_tensor_weights)."""
+    first, count = np.zeros(out, np.int32), np.zeros(out, np.int32)
+    w = np.zeros((out, TENSOR_MAX_TAPS), np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    check(lib().mp2vg_tensor_weights(src, out, first.ctypes.data_as(i32p), count.ctypes.data_as(i32p),
+                                     w.ctypes.data_as(i32p), TENSOR_MAX_TAPS), "tensor_weights")
+    return first, count, w[:, :int(count.max())]
 
 
 def geometry(width, height, chroma_format):

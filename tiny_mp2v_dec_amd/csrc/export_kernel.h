@@ -39,7 +39,8 @@ struct ExportSource {
     hipStream_t stream;  // the context's main stream
 };
 void export_source(const mp2vg_ctx* c, ExportSource* s);
-// device copy of a slot list, enqueued on the main stream (MP2VG status)
+// device copy of a slot list, enqueued on the main stream (MP2VG status); the tensor export
+// (tensor.cpp) sends its tap tables behind the slots in the same list
 int export_stage_slots(mp2vg_ctx* c, const int32_t* slots, int32_t n, const int32_t** d_slots);
 // after the kernel: the events the next export and the next batch decode wait on
 int export_enqueued(mp2vg_ctx* c);

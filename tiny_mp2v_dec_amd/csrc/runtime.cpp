@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -19,6 +20,7 @@
 #include "hipchk.h"
 #include "recon_kernel.h"
 #include "syntax.h"
+#include "tensor_kernel.h"
 
 namespace mp2vg {
 hipError_t launch_recon(int cf, int mcm, const KArgs& a, hipStream_t stream);
@@ -1706,6 +1708,125 @@ extern "C" int mp2vg_export_bytes(const mp2vg_config_t* cfg, const mp2vg_export_
     int32_t w, h;
     if (int rc = check_export(e, cfg->width, cfg->height, &w, &h)) return rc;
     *bytes = (uint64_t)n * 3 * (uint64_t)w * (uint64_t)h;
+    return MP2VG_OK;
+}
+
+// ---- tensor export, host-only side (include/mp2vg.h "tensor export"; kernel: tensor.hip) ---------
+
+static constexpr int32_t kTensorMaxOut = 16384;
+
+// Tap table of one axis in integers: with M = max(src, out), c = (2o + 1) src / (2 out) and
+// s = M / out, tap j has t_j = max(0, 2M - |(2j + 1) out - (2o + 1) src|) / (2M).
+extern "C" int mp2vg_tensor_weights(int32_t src, int32_t out, int32_t* first, int32_t* count, int32_t* weights,
+                                    int32_t max_taps) {
+    if (!first || !count || !weights || src < 1 || out < 1 || out > kTensorMaxOut || max_taps < 1 ||
+        (int64_t)src > 32 * (int64_t)out)
+        return MP2VG_E_INVALID;
+    const int64_t S = src, O = out, M = std::max(S, O);
+    for (int64_t o = 0; o < O; o++) {
+        const int64_t c2 = (2 * o + 1) * S;  // 2 out c
+        const int64_t lo = c2 - 2 * M + O, hi = c2 + 2 * M + O;
+        const int64_t f = lo < 0 ? 0 : lo / (2 * O), e = std::min(S, hi / (2 * O));
+        if (e - f < 1 || e - f > max_taps) {
+            set_error("tensor: an output has more taps than max_taps");
+            return MP2VG_E_INVALID;
+        }
+        int64_t sum = 0, best = f, tbest = -1;
+        for (int64_t j = f; j < e; j++) {
+            const int64_t d = (2 * j + 1) * O - c2, t = std::max<int64_t>(0, 2 * M - (d < 0 ? -d : d));
+            sum += t;
+            if (t > tbest) tbest = t, best = j;
+        }
+        int32_t* w = weights + o * max_taps;
+        int64_t qsum = 0;
+        for (int64_t j = f; j < e; j++) {
+            const int64_t d = (2 * j + 1) * O - c2, t = std::max<int64_t>(0, 2 * M - (d < 0 ? -d : d));
+            const int64_t q = (t * 32768 + sum) / (2 * sum);
+            w[j - f] = (int32_t)q;
+            qsum += q;
+        }
+        w[best - f] += (int32_t)(16384 - qsum);
+        for (int64_t k = e - f; k < max_taps; k++) w[k] = 0;
+        first[o] = (int32_t)f;
+        count[o] = (int32_t)(e - f);
+    }
+    return MP2VG_OK;
+}
+
+namespace mp2vg {
+int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int32_t rect[4], int32_t* elem) {
+    int32_t k[5];
+    if (!t) return MP2VG_E_INVALID;
+    const bool whole = !t->src_w && !t->src_h;
+    const int64_t sw = whole ? coded_w : t->src_w, sh = whole ? coded_h : t->src_h;
+    const char* why = nullptr;
+    if (t->layout != MP2VG_EXPORT_RGB_PLANAR && t->layout != MP2VG_EXPORT_RGB_PACKED) why = "layout";
+    else if (t->chroma != MP2VG_EXPORT_CHROMA_NEAREST && t->chroma != MP2VG_EXPORT_CHROMA_LINEAR) why = "chroma mode";
+    else if (mp2vg_export_coefficients(t->matrix, k) != MP2VG_OK) why = "matrix code";
+    else if (t->dtype < MP2VG_TENSOR_U8 || t->dtype > MP2VG_TENSOR_F32) why = "dtype";
+    else if (t->reserved[0] || t->reserved[1] || t->reserved[2] || t->reserved[3]) why = "reserved fields";
+    else if (t->src_x < 0 || t->src_y < 0 || sw < 1 || sh < 1 || (whole && (t->src_x || t->src_y)) ||
+             t->src_x + sw > coded_w || t->src_y + sh > coded_h)
+        why = "source rectangle";
+    else if (t->out_w < 1 || t->out_h < 1 || t->out_w > kTensorMaxOut || t->out_h > kTensorMaxOut) why = "output size";
+    else if (sw > 32 * (int64_t)t->out_w || sh > 32 * (int64_t)t->out_h) why = "ratio (above 32)";
+    else
+        for (int c = 0; c < 3 && !why; c++) {
+            if (!std::isfinite(t->scale[c]) || !std::isfinite(t->bias[c])) why = "scale / bias (not finite)";
+            else if (t->dtype == MP2VG_TENSOR_U8 && (t->scale[c] != 1.0f || t->bias[c] != 0.0f))
+                why = "scale / bias (U8 takes 1 and 0)";
+        }
+    if (why) {
+        set_error(std::string("tensor: bad ") + why);
+        return MP2VG_E_INVALID;
+    }
+    rect[0] = t->src_x, rect[1] = t->src_y, rect[2] = (int32_t)sw, rect[3] = (int32_t)sh;
+    *elem = t->dtype == MP2VG_TENSOR_U8 ? 1 : t->dtype == MP2VG_TENSOR_F32 ? 4 : 2;
+    return MP2VG_OK;
+}
+
+int tensor_tables(const int32_t rect[4], int32_t out_w, int32_t out_h, size_t lead, TensorTables* tt) {
+    std::vector<int32_t> first[2], count[2], w[2];
+    int32_t maxc[2];
+    for (int ax = 0; ax < 2; ax++) {
+        const int32_t src = rect[2 + ax], out = ax ? out_h : out_w;
+        first[ax].resize(out), count[ax].resize(out), w[ax].resize((size_t)out * MP2VG_TENSOR_MAX_TAPS);
+        if (int rc = mp2vg_tensor_weights(src, out, first[ax].data(), count[ax].data(), w[ax].data(),
+                                          MP2VG_TENSOR_MAX_TAPS))
+            return rc;
+        maxc[ax] = *std::max_element(count[ax].begin(), count[ax].end());
+    }
+    // segments of output columns whose taps share a window of kTensorSegCols source columns
+    std::vector<int32_t> segs;
+    for (int32_t o = 0; o < out_w;) {
+        const int32_t base = first[0][o];
+        int32_t e = o, last = base;
+        while (e < out_w && first[0][e] + count[0][e] <= base + kTensorSegCols) last = first[0][e] + count[0][e], e++;
+        segs.insert(segs.end(), {o, e, base, (last - base + 3) / 4});
+        o = e;
+    }
+    tt->nsegs = (int32_t)(segs.size() / 4), tt->hmax = maxc[0], tt->vmax = maxc[1];
+    std::vector<int32_t>& b = tt->blob;
+    b.assign(lead, 0);
+    auto put = [&](int i, const std::vector<int32_t>& v) { tt->off[i] = b.size(), b.insert(b.end(), v.begin(), v.end()); };
+    auto put_w = [&](int i, int ax, int32_t out) {  // rows of MP2VG_TENSOR_MAX_TAPS compacted to the axis' longest
+        tt->off[i] = b.size();
+        for (int32_t o = 0; o < out; o++)
+            b.insert(b.end(), w[ax].begin() + (size_t)o * MP2VG_TENSOR_MAX_TAPS,
+                     w[ax].begin() + (size_t)o * MP2VG_TENSOR_MAX_TAPS + maxc[ax]);
+    };
+    put(0, segs), put(1, first[0]), put_w(2, 0, out_w);
+    put(3, first[1]), put(4, count[1]), put_w(5, 1, out_h);
+    return MP2VG_OK;
+}
+}  // namespace mp2vg
+
+extern "C" int mp2vg_tensor_bytes(const mp2vg_config_t* cfg, const mp2vg_tensor_t* t, int32_t n, uint64_t* bytes) {
+    if (!cfg || !bytes || n <= 0 || mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK)
+        return MP2VG_E_INVALID;
+    int32_t rect[4], elem;
+    if (int rc = check_tensor(t, cfg->width, cfg->height, rect, &elem)) return rc;
+    *bytes = (uint64_t)n * 3 * (uint64_t)t->out_w * (uint64_t)t->out_h * (uint64_t)elem;
     return MP2VG_OK;
 }
 

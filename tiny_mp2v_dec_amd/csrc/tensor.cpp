@@ -1,0 +1,128 @@
+// tensor.cpp — host entry points of the tensor export that enqueue the kernel (tensor.hip):
+// mp2vg_tensor_slots and mp2vg_tensor_planes.  The host-only part (tap tables, validation, sizes)
+// lives in runtime.cpp; the context's side (slot table, staging ring, events) is the RGB export's.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+
+#include "export_kernel.h"
+#include "hipchk.h"
+#include "syntax.h"
+#include "tensor_kernel.h"
+
+using namespace mp2vg;
+
+static constexpr int32_t kTensorMaxFrames = 65535;  // the frame index is a grid dimension
+
+// coefficients, rectangle, normalisation and the tables at d (the device copy of tt.blob)
+static void tensor_args(TensorArgs* a, const mp2vg_tensor_t* t, const int32_t rect[4], const TensorTables& tt,
+                        const int32_t* d, void* dst) {
+    int32_t k[5];
+    mp2vg_export_coefficients(t->matrix, k);
+    a->cy = k[0], a->crv = k[1], a->cgu = k[2], a->cgv = k[3], a->cbu = k[4];
+    const int32_t base = 8192 - 16 * k[0];
+    a->kr = base - 128 * k[1];
+    a->kg = base - 128 * (k[2] + k[3]);
+    a->kb = base - 128 * k[4];
+    a->src_x = rect[0], a->src_y = rect[1];
+    a->out_w = t->out_w, a->out_h = t->out_h;
+    a->segs = d + tt.off[0], a->hfirst = d + tt.off[1], a->hw = d + tt.off[2];
+    a->vfirst = d + tt.off[3], a->vcount = d + tt.off[4], a->vw = d + tt.off[5];
+    a->hmax = tt.hmax, a->vmax = tt.vmax;
+    for (int c = 0; c < 3; c++) a->scale[c] = t->scale[c], a->bias[c] = t->bias[c];
+    a->dst = dst;
+}
+
+static int check_dst(const mp2vg_tensor_t* t, int32_t n, int32_t elem, const void* dst, uint64_t dst_bytes) {
+    if (dst_bytes != (uint64_t)n * 3 * (uint64_t)t->out_w * (uint64_t)t->out_h * (uint64_t)elem) {
+        set_error("tensor: dst_bytes is not n * 3 * out_w * out_h * element size");
+        return MP2VG_E_INVALID;
+    }
+    if ((uintptr_t)dst % (uintptr_t)elem) {
+        set_error("tensor: dst is not aligned to the element size");
+        return MP2VG_E_INVALID;
+    }
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t n, const mp2vg_tensor_t* t, void* dst,
+                                  uint64_t dst_bytes) {
+    if (!c || !slots || !t || !dst || n <= 0 || n > kTensorMaxFrames) return MP2VG_E_INVALID;
+    ExportSource s;
+    export_source(c, &s);
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= s.nslots) {
+            set_error("tensor: slot out of range");
+            return MP2VG_E_INVALID;
+        }
+    int32_t rect[4], elem;
+    if (int rc = check_tensor(t, s.pw, s.ph, rect, &elem)) return rc;
+    if (int rc = check_dst(t, n, elem, dst, dst_bytes)) return rc;
+    TensorTables tt;
+    if (int rc = tensor_tables(rect, t->out_w, t->out_h, (size_t)n, &tt)) return rc;
+    memcpy(tt.blob.data(), slots, sizeof(int32_t) * n);
+    HIPCHK(hipSetDevice(s.device));
+    TensorArgs a;
+    memset(&a, 0, sizeof a);
+    const int32_t* d = nullptr;
+    if (int rc = export_stage_slots(c, tt.blob.data(), (int32_t)tt.blob.size(), &d)) return rc;
+    a.slots = d;
+    a.ftab = s.ftab;
+    for (int p = 0; p < 3; p++) {
+        a.plane_off[p] = s.plane_off[p];
+        a.stride[p] = s.stride[p];
+    }
+    a.cw = s.cw;
+    a.ch = s.ch;
+    tensor_args(&a, t, rect, tt, d, dst);
+    // the list's copy is in flight: its events are recorded whether or not the launch succeeded
+    const hipError_t le = launch_tensor(s.cf, t->layout, t->chroma, t->dtype, a, tt.nsegs, n, s.stream);
+    const int rc = export_enqueued(c);
+    HIPCHK(le);
+    return rc;
+}
+
+extern "C" int mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3], int32_t cf,
+                                   int32_t coded_w, int32_t coded_h, const mp2vg_tensor_t* t, void* dst,
+                                   uint64_t dst_bytes) {
+    if (!planes || !stride || !t || !dst || device < 0 || cf < 1 || cf > 3 || coded_w <= 0 || coded_h <= 0)
+        return MP2VG_E_INVALID;
+    if ((cf < 3 && (coded_w & 1)) || (cf == 1 && (coded_h & 1))) {
+        set_error("tensor: odd coded size with subsampled chroma");
+        return MP2VG_E_INVALID;
+    }
+    const int32_t cw = cf == 3 ? coded_w : coded_w >> 1, ch = cf == 1 ? coded_h >> 1 : coded_h;
+    for (int p = 0; p < 3; p++)
+        if (!planes[p] || ((uintptr_t)planes[p] & 3) || stride[p] < 4 || (stride[p] & 3) ||
+            stride[p] < (p ? cw : coded_w)) {
+            set_error("tensor: planes must be 4-byte aligned, strides multiples of 4 and at least the plane width");
+            return MP2VG_E_INVALID;
+        }
+    int32_t rect[4], elem;
+    if (int rc = check_tensor(t, coded_w, coded_h, rect, &elem)) return rc;
+    if (int rc = check_dst(t, 1, elem, dst, dst_bytes)) return rc;
+    TensorTables tt;
+    if (int rc = tensor_tables(rect, t->out_w, t->out_h, 0, &tt)) return rc;
+    HIPCHK(hipSetDevice(device));
+    int32_t* d = nullptr;
+    const size_t bytes = tt.blob.size() * sizeof(int32_t);
+    HIPCHK(hipMalloc((void**)&d, bytes));
+    hipError_t e = hipMemcpy(d, tt.blob.data(), bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        TensorArgs a;
+        memset(&a, 0, sizeof a);
+        for (int p = 0; p < 3; p++) {
+            a.planes[p] = planes[p];
+            a.stride[p] = stride[p];
+        }
+        a.cw = cw;
+        a.ch = ch;
+        tensor_args(&a, t, rect, tt, d, dst);
+        e = launch_tensor(cf, t->layout, t->chroma, t->dtype, a, tt.nsegs, 1, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    hipFree(d);
+    HIPCHK(e);
+    return MP2VG_OK;
+}

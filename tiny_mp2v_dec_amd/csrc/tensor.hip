@@ -1,0 +1,215 @@
+// tensor.hip — decoded frames to cropped, antialias-resized, normalised model-input tensors on the
+// device (gfx950 / CDNA4), one launch per batch, no full-size RGB intermediate in memory.
+//
+// The arithmetic is the bit-exact contract of include/mp2vg.h ("tensor export"): the RGB export's
+// 8-bit R'G'B' of the whole coded frame, cropped, then the triangle filter with 14-bit integer
+// weights (host tables, mp2vg_tensor_weights), vertical pass first, then horizontal, then
+// fmaf(Q / 64, scale, bias) and one round-to-nearest-even cast.
+//
+// Work split: a workgroup of 256 lanes owns two adjacent output rows of one frame (blockIdx.y,
+// blockIdx.z; the last row of an odd height alone) and one segment of their columns (blockIdx.x; a
+// segment is the run of output columns whose taps fit a window of kTensorSegCols = 2048 source
+// columns, so a 1920-wide source is one segment).
+//   vertical pass: a lane takes 4 source columns (a unit, as in export.hip: unaligned dword loads
+//       clamped into the plane row, chroma taps of the RGB export) and walks the union of the two
+//       rows' source rows, converting each to R'G'B' in registers once and accumulating qv P for
+//       both output rows in 2 x 12 int32 (adjacent rows share half their taps when downscaling,
+//       nearly all when upscaling); the rounded V values (0..16320) are parked in LDS as int16,
+//       [2][3][2048]: 24 KB per workgroup whatever the ratio, one 8-byte store per row and channel.
+//   horizontal pass: after one barrier, a lane takes one output element (row, pixel, channel),
+//       sums its taps from LDS (every lane the axis' longest count, over zero-padded weights: a
+//       uniform, unrolled loop keeps several tap loads in flight), normalises, casts and stores the
+//       element (coalesced along the row; the output is small, so element stores do not matter:
+//       dst needs element alignment only).
+// When downscaling, a source row is still converted by about 1.5 workgroups and read that often
+// (from L2 mostly), against write + read of 3 B/pixel RGB and a 12 B/pixel float intermediate on
+// the unfused path.
+//
+// Static resources (hipcc -O3, --offload-arch=gfx950, all 40 variants): 60-68 VGPRs, no scratch,
+// 24576 B LDS per workgroup, which sets 6 waves per SIMD (measured speed, also of the one-row
+// split this replaced: profiles/export/tensor.md).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mp2vg.h"
+#include "export_pixels.h"
+#include "tensor_kernel.h"
+
+namespace mp2vg {
+
+// R, G, B (0..255) of pixels x0 .. x0 + 3: the RGB export's pixels4, unpacked
+template <int CF, bool LINEAR>
+__device__ __forceinline__ void rgb4(const TensorArgs& a, const Rows& r, int x0, int R[4], int G[4], int B[4]) {
+    const uint32_t yv = load4(r.y, x0, a.stride[0]);
+    int cb[4], cr[4];
+    chroma4<CF, LINEAR>(r.cb, r.cb1, x0, a.stride[1], a.cw, cb);
+    chroma4<CF, LINEAR>(r.cr, r.cr1, x0, a.stride[2], a.cw, cr);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int yy = __mul24(a.cy, byte_of(yv, i));
+        const int tr = __mul24(a.crv, cr[i]) + a.kr;
+        const int tg = __mul24(a.cgu, cb[i]) + __mul24(a.cgv, cr[i]) + a.kg;
+        const int tb = __mul24(a.cbu, cb[i]) + a.kb;
+        R[i] = (int)clamp8((yy + tr) >> 14);
+        G[i] = (int)clamp8((yy + tg) >> 14);
+        B[i] = (int)clamp8((yy + tb) >> 14);
+    }
+}
+
+struct alignas(8) V4 {
+    int16_t v[4];
+};
+
+// float32 to bfloat16 bits, round to nearest even (the value is never NaN: scale and bias are finite)
+__device__ __forceinline__ uint16_t bf16_rne(float f) {
+    uint32_t u = __float_as_uint(f);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+template <int CF, bool LINEAR, bool PACKED, int DTYPE>
+__global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
+    __shared__ alignas(8) int16_t lds[2][3][kTensorSegCols];
+    const int tid = (int)threadIdx.x;
+    const int oy = 2 * (int)blockIdx.y;         // output rows oy and, unless oy is the last, oy + 1
+    const bool two = oy + 1 < a.out_h;
+    const size_t f = blockIdx.z;
+    const int32_t* seg = a.segs + 4 * blockIdx.x;
+    const int o_begin = seg[0], o_end = seg[1], base = seg[2], nunits = seg[3];
+    const uint8_t* pl[3];
+#pragma unroll
+    for (int p = 0; p < 3; p++) pl[p] = a.slots ? (const uint8_t*)a.ftab[a.slots[f]] + a.plane_off[p] : a.planes[p];
+
+    // vertical pass over the union of the two rows' source rows (vfirst and the range ends never
+    // decrease with the output row); a row outside one output row's taps has weight 0 there
+    const int f0 = a.vfirst[oy], c0 = a.vcount[oy];
+    const int f1 = two ? a.vfirst[oy + 1] : f0, c1 = two ? a.vcount[oy + 1] : 0;
+    const int nrows = max(f0 + c0, f1 + c1) - f0;
+    const int32_t* qv0 = a.vw + (size_t)oy * a.vmax;
+    const int32_t* qv1 = qv0 + (two ? a.vmax : 0);
+    for (int u = tid; u < nunits; u += 256) {
+        const int x0 = a.src_x + base + 4 * u;
+        int aR[2][4] = {}, aG[2][4] = {}, aB[2][4] = {};
+        for (int k = 0; k < nrows; k++) {
+            const int y = a.src_y + f0 + k;
+            Rows r;
+            const int j = CF == 1 ? y >> 1 : y;
+            const int j1 = CF == 1 && LINEAR ? min(max(j + ((y & 1) ? 1 : -1), 0), a.ch - 1) : j;
+            r.y = pl[0] + (size_t)y * a.stride[0];
+            r.cb = pl[1] + (size_t)j * a.stride[1];
+            r.cr = pl[2] + (size_t)j * a.stride[2];
+            r.cb1 = pl[1] + (size_t)j1 * a.stride[1];
+            r.cr1 = pl[2] + (size_t)j1 * a.stride[2];
+            int R[4], G[4], B[4];
+            rgb4<CF, LINEAR>(a, r, x0, R, G, B);
+            const int k1 = f0 + k - f1;
+            const int q0 = k < c0 ? qv0[k] : 0;
+            const int q1 = k1 >= 0 && k1 < c1 ? qv1[k1] : 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                aR[0][i] += __mul24(q0, R[i]), aR[1][i] += __mul24(q1, R[i]);
+                aG[0][i] += __mul24(q0, G[i]), aG[1][i] += __mul24(q1, G[i]);
+                aB[0][i] += __mul24(q0, B[i]), aB[1][i] += __mul24(q1, B[i]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            V4 vr, vg, vb;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                vr.v[i] = (int16_t)((aR[t][i] + 128) >> 8);
+                vg.v[i] = (int16_t)((aG[t][i] + 128) >> 8);
+                vb.v[i] = (int16_t)((aB[t][i] + 128) >> 8);
+            }
+            *(V4*)&lds[t][0][4 * u] = vr;
+            *(V4*)&lds[t][1][4 * u] = vg;
+            *(V4*)&lds[t][2][4 * u] = vb;
+        }
+    }
+    __syncthreads();
+
+    // horizontal pass: one output element (row, pixel, channel) per lane
+    const int nout = o_end - o_begin;
+    const size_t w = (size_t)a.out_w, h = (size_t)a.out_h;
+    for (int idx = tid; idx < (two ? 6 : 3) * nout; idx += 256) {
+        const int t = idx >= 3 * nout ? 1 : 0, e = idx - 3 * nout * t;
+        int c, o;
+        if (PACKED) {
+            o = e / 3;
+            c = e - 3 * o;
+        } else {
+            c = e >= 2 * nout ? 2 : e >= nout ? 1 : 0;
+            o = e - c * nout;
+        }
+        o += o_begin;
+        // every lane runs the axis' longest tap count, so the loads of several taps are in flight:
+        // the table's rows are zero from the column's tap count on, and a V index past the window is clamped (its
+        // weight is zero, whatever the LDS holds there)
+        const int16_t* v = &lds[t][c][0];
+        const int v0 = a.hfirst[o] - base;
+        const int32_t* qh = a.hw + (size_t)o * a.hmax;
+        int sum = 8192;
+#pragma unroll 4
+        for (int k = 0; k < a.hmax; k++) sum += __mul24(qh[k], (int)v[min(v0 + k, kTensorSegCols - 1)]);
+        const int Q = sum >> 14;
+        const size_t y = (size_t)(oy + t);
+        const size_t at = PACKED ? ((f * h + y) * w + (size_t)o) * 3 + (size_t)c
+                                 : ((f * 3 + (size_t)c) * h + y) * w + (size_t)o;
+        if (DTYPE == MP2VG_TENSOR_U8) {
+            ((uint8_t*)a.dst)[at] = (uint8_t)((Q + 32) >> 6);
+        } else {
+            const float sc = c == 0 ? a.scale[0] : c == 1 ? a.scale[1] : a.scale[2];
+            const float bi = c == 0 ? a.bias[0] : c == 1 ? a.bias[1] : a.bias[2];
+            const float x = __builtin_fmaf((float)Q * 0.015625f, sc, bi);  // Q / 64 is exact
+            if (DTYPE == MP2VG_TENSOR_F32)
+                ((float*)a.dst)[at] = x;
+            else if (DTYPE == MP2VG_TENSOR_F16)
+                ((_Float16*)a.dst)[at] = (_Float16)x;  // v_cvt_f16_f32: round to nearest even
+            else
+                ((uint16_t*)a.dst)[at] = bf16_rne(x);
+        }
+    }
+}
+
+template <int CF, bool LINEAR, bool PACKED>
+static void launch_dtype(int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
+    const dim3 block(256, 1, 1);
+    if (dtype == MP2VG_TENSOR_U8)
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8>), grid, block, 0, stream, a);
+    else if (dtype == MP2VG_TENSOR_F16)
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16>), grid, block, 0, stream, a);
+    else if (dtype == MP2VG_TENSOR_BF16)
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16>), grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32>), grid, block, 0, stream, a);
+}
+
+template <int CF>
+static void launch_cf(int layout, int chroma, int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
+    const bool lin = chroma == MP2VG_EXPORT_CHROMA_LINEAR && CF != 3;  // 4:4:4: LINEAR is NEAREST
+    if (layout == MP2VG_EXPORT_RGB_PACKED) {
+        if (lin)
+            launch_dtype<CF, CF != 3, true>(dtype, a, grid, stream);
+        else
+            launch_dtype<CF, false, true>(dtype, a, grid, stream);
+    } else {
+        if (lin)
+            launch_dtype<CF, CF != 3, false>(dtype, a, grid, stream);
+        else
+            launch_dtype<CF, false, false>(dtype, a, grid, stream);
+    }
+}
+
+hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, const TensorArgs& a, int nsegs, int n,
+                         hipStream_t stream) {
+    const dim3 grid((unsigned)nsegs, (unsigned)((a.out_h + 1) / 2), (unsigned)n);
+    if (cf == 1)
+        launch_cf<1>(layout, chroma, dtype, a, grid, stream);
+    else if (cf == 2)
+        launch_cf<2>(layout, chroma, dtype, a, grid, stream);
+    else
+        launch_cf<3>(layout, chroma, dtype, a, grid, stream);
+    return hipGetLastError();
+}
+
+}  // namespace mp2vg

@@ -1,0 +1,57 @@
+// tensor_kernel.h — arguments of the tensor export kernel (tensor.hip), shared with its host entry
+// points (tensor.cpp: mp2vg_tensor_slots / mp2vg_tensor_planes) and the host-only side of the
+// contract (runtime.cpp: tap tables, validation, sizes).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/mp2vg.h"
+
+namespace mp2vg {
+
+// source columns one workgroup keeps in LDS (the V rows of its two output rows, 3 channels of
+// int16 each: 24 KB)
+constexpr int kTensorSegCols = 2048;
+
+// One launch exports n frames.  Planes as in ExportArgs; every table is int32 in device memory.
+//   segs[4 s ..]: output columns [o_begin, o_end) of segment s, the first source column `base` any
+//                 of them reads (relative to the rectangle) and the 4-pixel units that cover the
+//                 columns base .. the last one read; every tap range of the segment lies inside
+//                 [base, base + kTensorSegCols)
+//   hfirst / hw: horizontal taps of output column o: hw[o * hmax + k], zero from the column's tap
+//                 count on (the kernel runs all hmax); vfirst / vcount / vw: the rows'
+struct TensorArgs {
+    const uint64_t* ftab;
+    const int32_t* slots;
+    const uint8_t* planes[3];
+    uint32_t plane_off[3];
+    int32_t stride[3];
+    int32_t cw, ch;
+    int32_t cy, crv, cgu, cgv, cbu, kr, kg, kb;  // as ExportArgs
+    int32_t src_x, src_y;                        // top-left of the source rectangle
+    int32_t out_w, out_h;
+    const int32_t *segs, *hfirst, *hw, *vfirst, *vcount, *vw;
+    int32_t hmax, vmax;
+    float scale[3], bias[3];
+    void* dst;
+};
+
+// cf 1..3; layout, chroma, dtype of the mp2vg_tensor_t; grid = (nsegs, row pairs, n)
+hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, const TensorArgs& a, int nsegs, int n,
+                         hipStream_t stream);
+
+// host-only side (runtime.cpp)
+// checks t against a coded size; the source rectangle in rect[4] (x, y, w, h) and the element size
+int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int32_t rect[4], int32_t* elem);
+// The int32 tables of a validated tensor export, behind `lead` entries left for the caller (the
+// slot list): segs, hfirst, hw, vfirst, vcount, vw.  off[6] = the index of each in blob.
+struct TensorTables {
+    std::vector<int32_t> blob;
+    size_t off[6];
+    int32_t nsegs, hmax, vmax;
+};
+int tensor_tables(const int32_t rect[4], int32_t out_w, int32_t out_h, size_t lead, TensorTables* tt);
+
+}  // namespace mp2vg

@@ -105,6 +105,22 @@ class frame_c:  # noqa: N801  (reference name)
                                         ctypes.c_void_p(t.data_ptr()), t.numel()), "export_planes")
         return t
 
+    def export_tensor(self, size, crop=None, dtype="float16", mean=None, std=None, layout="nchw", chroma="linear",
+                      matrix=1, out=None):
+        """This frame as a cropped, resized, normalised model-input tensor on its device, (1, 3, h,
+        w) or (1, h, w, 3) (mp2vg_tensor_planes; arguments as DeviceContext.export_tensor).
+        Device frames only; complete on return, so the tensor outlives the callback."""
+        if not self.is_device:
+            raise ValueError("host frame: export_tensor needs a device_frames=True decoder")
+        f = self._f
+        cf = 3 if f.width[1] == f.width[0] else (2 if f.height[1] == f.height[0] else 1)
+        t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
+        o = _lib.tensor_out(out, _lib.tensor_shape(t, 1), dtype, f.device)
+        planes = (ctypes.c_void_p * 3)(*[self.device_ptr(i) for i in range(3)])
+        check(lib().mp2vg_tensor_planes(f.device, planes, f.stride, cf, f.width[0], f.height[0], ctypes.byref(t),
+                                        ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()), "tensor_planes")
+        return o
+
     def get_strides(self, i):
         return self._f.stride[i]
 

@@ -249,6 +249,32 @@ class DeviceContext:
             self.synchronize()
         return t
 
+    def export_tensor(self, slots, size, crop=None, dtype="float16", mean=None, std=None, layout="nchw",
+                      chroma="linear", matrix=1, out=None, sync=True):
+        """Frames of `slots` (any order, repeats allowed) as one model-input tensor on this
+        context's device (mp2vg_tensor_slots: one fused kernel launch): cropped to crop = (x, y, w,
+        h) in luma pixels (None: the coded frame), resized to size = (width, height) with the
+        bit-exact antialiased triangle filter of include/mp2vg.h, normalised per channel and cast to
+        dtype (torch.float16 / "float16", bfloat16, float32 or uint8).  With mean / std (0..1
+        units) the value is (x / 255 - mean) / std, computed as fmaf(x, scale, bias) with scale =
+        float32(1 / (255 std)), bias = float32(-mean / std); without them x / 255 (uint8: x).
+        (n, 3, h, w) for layout "nchw", (n, h, w, 3) for "nhwc"; chroma and matrix as export_rgb.
+        Writes into `out` when given.
+
+        Stream ordering is export_rgb's: the export runs on the context's own stream behind the
+        decodes enqueued so far; work torch has enqueued on `out` must have finished before the
+        call, and with sync=False torch must not read the tensor before synchronize().  At most
+        65535 slots per call."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
+        o = _lib.tensor_out(out, _lib.tensor_shape(t, len(slots)), dtype, self.cfg.device)
+        check(lib().mp2vg_tensor_slots(self.h, slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(slots),
+                                       ctypes.byref(t), ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()),
+              "tensor_slots")
+        if sync:
+            self.synchronize()
+        return o
+
     def digests(self, slots):
         slots = np.ascontiguousarray(slots, np.int32)
         out = np.zeros(len(slots), np.uint64)
@@ -292,6 +318,37 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
             part = parsed.display[i:i + EXPORT_MAX_FRAMES]
             ctx.export_rgb(part, out=out[i:i + len(part)], layout=layout, chroma=chroma, matrix=matrix, size=size,
                            sync=False)
+        ctx.synchronize()
+        return out
+
+
+def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
+                  layout="nchw", chroma="linear", matrix=None, device=0):
+    """Decode a whole elementary stream (coded size width x height) and return its pictures in
+    display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
+    dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
+    horizontal_size_value x vertical_size_value at the top left when these are set and no larger
+    than the coded size, else the coded frame; matrix=None takes the stream's matrix_coefficients.
+    A stream without pictures gives an empty tensor, and one of more than 65535 pictures is
+    exported in several calls."""
+    parsed = Parsed(es, width, height, chroma_format)
+    sh = parsed.headers.sequence_header
+    w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
+    if crop is None and 0 < w <= width and 0 < h <= height:
+        crop = (0, 0, w, h)
+    if matrix is None:
+        matrix = export_matrix(parsed.headers)
+    t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
+    out = _lib.tensor_out(None, _lib.tensor_shape(t, parsed.npics), dtype, device)
+    if not parsed.npics:
+        return out
+    with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
+        ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        ctx.decode()
+        for i in range(0, parsed.npics, EXPORT_MAX_FRAMES):  # mp2vg_tensor_slots takes 65535 per call
+            part = parsed.display[i:i + EXPORT_MAX_FRAMES]
+            ctx.export_tensor(part, size, crop=crop, dtype=dtype, mean=mean, std=std, layout=layout, chroma=chroma,
+                              matrix=matrix, out=out[i:i + len(part)], sync=False)
         ctx.synchronize()
         return out
 
