@@ -94,7 +94,9 @@ class mp2v_decoder_c {
 public:
     mp2v_decoder_c() = default;
     // flags: MP2VG_DECODER_DEVICE_FRAMES hands frames over in HBM (get_planes() then returns
-    // device pointers); 0 keeps the reference's host frame_c contract
+    // device pointers); MP2VG_DECODER_DEVICE_PARSE (= kDeviceParse) parses the slices on the device
+    // instead of on host threads; 0 keeps the reference's host frame_c contract
+    static constexpr int kDeviceParse = MP2VG_DECODER_DEVICE_PARSE;
     mp2v_decoder_c(const decoder_config_t& config, std::function<void(frame_c*)> renderer, int device = 0,
                    int flags = 0) {
         decoder_init(config, renderer, device, flags);

@@ -133,6 +133,11 @@ typedef struct mp2vg_config {
  * (default: closed groups of pictures dealt to 2 streams, or MP2VG_STREAMS), so per-launch
  * device times never overlap -- per-kernel roofline measurements and their rocprof traces */
 #define MP2VG_CTX_ONE_STREAM 2
+/* mp2vg_config_t.reserved flag for mp2vg_decoder_create (opt-in): decode() only scans the stream
+ * on the host (mp2vg_scan_es) and feeds its 16-picture chunks through mp2vg_batch_upload_es, so the
+ * slices are parsed on the device and no parse workers start.  Display order, the frame pool,
+ * host or device frames and the lanes of mp2vg_decoder_create_multi are unchanged. */
+#define MP2VG_DECODER_DEVICE_PARSE 4
 
 typedef struct mp2vg_ctx mp2vg_ctx_t;
 
@@ -452,6 +457,54 @@ int  mp2vg_parsed_stream_headers(const mp2vg_parsed_t* p, mp2vg_stream_headers_t
  * number of shards. */
 int  mp2vg_parsed_shards(const mp2vg_parsed_t* p, int32_t* shard, int32_t n);
 void mp2vg_parsed_free(mp2vg_parsed_t* p);
+
+/* ---- host scan + device parse ------------------------------------------------------------
+ * mp2vg_scan_es is pass 1 of mp2vg_parse_es on its own: start codes, headers, picture records
+ * with W matrices, references, display order, GOP index, shards and stream headers, plus a slice
+ * table (picture, macroblock row, byte range) and the few header fields per picture the
+ * macroblock syntax depends on.  It rejects what mp2vg_parse_es rejects at picture level, and
+ * itself makes the host emitter's three row rejections (slice row outside the picture, two slices
+ * in one macroblock row, row not covered by any slice; MP2VG_E_UNSUPPORTED), so every slice of
+ * the table owns its row.  The scan keeps a pointer to buf: the stream must outlive it.
+ * mp2vg_batch_upload_es (below) sends the bitstream of a picture range to the device, where one
+ * lane per slice parses it into the records mp2vg_parse_es would have produced, byte for byte. */
+typedef struct mp2vg_scan mp2vg_scan_t;
+int  mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cfg, mp2vg_scan_t** out);
+int  mp2vg_scan_counts(const mp2vg_scan_t* s, int32_t* npics, uint64_t* nslices);
+const mp2vg_picture_t* mp2vg_scan_pictures(const mp2vg_scan_t* s);
+int  mp2vg_scan_display_order(const mp2vg_scan_t* s, int32_t* order, int32_t n);
+int  mp2vg_scan_gop_index(const mp2vg_scan_t* s, int32_t* gop, int32_t n);
+int  mp2vg_scan_shards(const mp2vg_scan_t* s, int32_t* shard, int32_t n);
+int  mp2vg_scan_stream_headers(const mp2vg_scan_t* s, mp2vg_stream_headers_t* out);
+void mp2vg_scan_free(mp2vg_scan_t* s);
+/* The CPU twin of the device parse (host only, no device needed): the kernels' own slice parser
+ * (csrc/slice_parse.h), slice by slice over pictures [first, first + npics) -- count pass,
+ * prefix sum, emit pass -- on a copy of the range's bitstream of exactly the device's size.
+ * With mbs = coefs = NULL it only counts: *nmbs_out and *ncoefs_out (either may be NULL) are the
+ * array sizes of the second call, which fills mbs[nmbs] and coefs[ncoefs] (both must equal the
+ * counts) laid out as mp2vg_parse_es lays them out, picture `first` at record 0.  A rejected
+ * slice returns the host emitter's status and sets its message.  MP2VG_E_STATE is an internal
+ * failure (the iteration bound of a slice exceeded, or the two passes disagree). */
+int  mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32_t npics, mp2vg_mb_t* mbs, uint64_t nmbs,
+                           uint32_t* coefs, uint64_t ncoefs, uint64_t* nmbs_out, uint64_t* ncoefs_out);
+/* Upload pictures [first, first + npics) of a scanned stream as a record batch parsed on the
+ * device (parse.hip): the range's bitstream crosses to HBM, a count pass (one lane per slice)
+ * writes the MB records and counts each slice's coefficient words, a prefix sum lays the words
+ * out as mp2vg_parse_es does, and an emit pass writes them.  pics = NULL uses the scan's picture
+ * records with mb_first rebased to the range; otherwise pics[npics] are the range's records with
+ * the caller's slots and mb_first (picture i's records at mb_first, all inside npics pictures'
+ * worth of records).  Synchronous up to the count pass: a rejected slice returns the host
+ * emitter's status for the first failing slice in stream order, with its message in
+ * mp2vg_last_error(); no batch is then resident (mp2vg_batch_decode: MP2VG_E_STATE) and the
+ * context stays usable.  The resident batch decodes, exports and times like any other. */
+int  mp2vg_batch_upload_es(mp2vg_ctx_t* ctx, const mp2vg_scan_t* scan, const mp2vg_picture_t* pics,
+                           int32_t first, int32_t npics);
+/* sizes of the resident batch's record arrays, and a copy of them (synchronous; sizes must match) */
+int  mp2vg_batch_record_counts(mp2vg_ctx_t* ctx, uint64_t* nmbs, uint64_t* ncoefs);
+int  mp2vg_batch_download_records(mp2vg_ctx_t* ctx, mp2vg_mb_t* mbs, uint64_t nmbs, uint32_t* coefs,
+                                  uint64_t ncoefs);
+/* device times (ms, HIP events) of the last mp2vg_batch_upload_es: count pass, scan, emit pass */
+int  mp2vg_last_parse_times(mp2vg_ctx_t* ctx, float ms[3]);
 
 /* Conformance hook: decode one Annex B code (MSB-first 64-bit window: the code, then whatever
  * follows) with the emitter's own decoders.  Tables follow the reference's VLC decoders

@@ -141,6 +141,10 @@ EXPORTS = [
     "mp2vg_export_coefficients", "mp2vg_export_matrix", "mp2vg_export_bytes", "mp2vg_export_slots",
     "mp2vg_export_planes",
     "mp2vg_tensor_weights", "mp2vg_tensor_bytes", "mp2vg_tensor_slots", "mp2vg_tensor_planes",
+    "mp2vg_scan_es", "mp2vg_scan_counts", "mp2vg_scan_pictures", "mp2vg_scan_display_order",
+    "mp2vg_scan_gop_index", "mp2vg_scan_shards", "mp2vg_scan_stream_headers", "mp2vg_scan_free",
+    "mp2vg_scan_parse_host", "mp2vg_batch_upload_es", "mp2vg_batch_record_counts",
+    "mp2vg_batch_download_records", "mp2vg_last_parse_times",
 ]
 
 _lib = None
@@ -213,6 +217,19 @@ def lib():
         "mp2vg_tensor_bytes": ([P(Config), P(Tensor), I32, P(U64)], ctypes.c_int),
         "mp2vg_tensor_slots": ([VP, P(I32), I32, P(Tensor), VP, U64], ctypes.c_int),
         "mp2vg_tensor_planes": ([I32, P(VP), P(I32), I32, I32, I32, P(Tensor), VP, U64], ctypes.c_int),
+        "mp2vg_scan_es": ([VP, U64, P(Config), P(VP)], ctypes.c_int),
+        "mp2vg_scan_counts": ([VP, P(I32), P(U64)], ctypes.c_int),
+        "mp2vg_scan_pictures": ([VP], VP),
+        "mp2vg_scan_display_order": ([VP, P(I32), I32], ctypes.c_int),
+        "mp2vg_scan_gop_index": ([VP, P(I32), I32], ctypes.c_int),
+        "mp2vg_scan_shards": ([VP, P(I32), I32], ctypes.c_int),
+        "mp2vg_scan_stream_headers": ([VP, P(StreamHeaders)], ctypes.c_int),
+        "mp2vg_scan_free": ([VP], None),
+        "mp2vg_scan_parse_host": ([VP, I32, I32, VP, U64, VP, U64, P(U64), P(U64)], ctypes.c_int),
+        "mp2vg_batch_upload_es": ([VP, VP, VP, I32, I32], ctypes.c_int),
+        "mp2vg_batch_record_counts": ([VP, P(U64), P(U64)], ctypes.c_int),
+        "mp2vg_batch_download_records": ([VP, VP, U64, VP, U64], ctypes.c_int),
+        "mp2vg_last_parse_times": ([VP, P(ctypes.c_float)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -230,6 +247,7 @@ def check(status, what):
 
 
 MP2VG_DECODER_DEVICE_FRAMES, MP2VG_CTX_ONE_STREAM = 1, 2  # mp2vg_config_t.reserved flags
+MP2VG_DECODER_DEVICE_PARSE = 4  # drop-in decoder: slices parsed on the device (mp2vg_batch_upload_es)
 
 
 def make_config(width, height, chroma_format, pool=10, threads=0, reordering=True, device=0, flags=0):

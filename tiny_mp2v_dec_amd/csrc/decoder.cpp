@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "recon_kernel.h"
+#include "scan.h"
 #include "syntax.h"
 
 using namespace mp2vg;
@@ -219,6 +220,7 @@ struct mp2vg_decoder {
     std::vector<std::unique_ptr<Lane>> lanes;
     std::unique_ptr<FramePool> hpool;  // pinned host frames, shared by every lane
     bool device_frames = false;        // MP2VG_DECODER_DEVICE_FRAMES: frames handed over in HBM
+    bool device_parse = false;         // MP2VG_DECODER_DEVICE_PARSE: slices parsed on the device
     // host frames by the copy kernel: every lane on one device (the pinned pool is mapped for the
     // device it was allocated under; lanes on several devices copy by DMA)
     bool kernel_copy = false;
@@ -246,7 +248,7 @@ extern "C" int mp2vg_decoder_create_multi(const mp2vg_config_t* cfg, const int32
                                           mp2vg_render_fn fn, void* user, mp2vg_decoder_t** out) {
     if (!cfg || !fn || !out || !devices || ndevices < 1 || ndevices > 64) return MP2VG_E_INVALID;
     *out = nullptr;
-    if (cfg->reserved & ~MP2VG_DECODER_DEVICE_FRAMES) {
+    if (cfg->reserved & ~(MP2VG_DECODER_DEVICE_FRAMES | MP2VG_DECODER_DEVICE_PARSE)) {
         set_error("unknown decoder flags in mp2vg_config_t.reserved");
         return MP2VG_E_INVALID;
     }
@@ -258,6 +260,7 @@ extern "C" int mp2vg_decoder_create_multi(const mp2vg_config_t* cfg, const int32
     d->user = user;
     d->g.init(cfg->width, cfg->height, cfg->chroma_format);
     d->device_frames = cfg->reserved & MP2VG_DECODER_DEVICE_FRAMES;
+    d->device_parse = cfg->reserved & MP2VG_DECODER_DEVICE_PARSE;
     // (opt-in, MP2VG_PIN=1: on a shared 2-socket host it did not steady the slow decode() calls,
     // profiles/r6/dropin_pin_ab.txt)
     if (getenv("MP2VG_PIN") && atoi(getenv("MP2VG_PIN"))) {
@@ -299,7 +302,7 @@ extern "C" int mp2vg_decoder_create_multi(const mp2vg_config_t* cfg, const int32
         // chunk record buffers sized up front: every MB record of a chunk, and 32 coefficient
         // words per MB (the bench stream needs 12.5; a chunk that needs more grows its set once)
         bool ok = true;
-        for (int k = 0; k < 2; k++)
+        for (int k = 0; k < 2 && !d->device_parse; k++)  // (the device parse gathers no records on the host)
             ok = ok && L.mbuf[k].reserve(chunk_mbs * sizeof(mp2vg_mb_t)) && L.cbuf[k].reserve(chunk_mbs * 32 * 4);
         if (d->device_frames) {
             L.dpool.reset(new FramePool(d->g.slot_bytes, true, L.device));
@@ -391,20 +394,30 @@ static int decoder_decode(mp2vg_decoder_t* d, const uint8_t* buf, uint64_t len) 
     double t0 = now_ms(), tc;
     double t_up = 0, t_dec = 0, t_down = 0, t_wait = 0, t_gather = 0;
     ParseSession* ps = nullptr;
+    // MP2VG_DECODER_DEVICE_PARSE: the host only scans (start codes, headers, slice table); no parse
+    // workers start, and each chunk's slices are parsed on its lane's device (mp2vg_batch_upload_es)
+    mp2vg_scan_t* scan = nullptr;
+    if (d->device_parse) {
+        const int rc = mp2vg_scan_es(buf, len, &d->cfg, &scan);
+        t0 = trace_phase("dropin: scan", t0);
+        if (rc != MP2VG_OK) return rc;
+    }
+    std::unique_ptr<mp2vg_scan_t, void (*)(mp2vg_scan_t*)> scan_guard(scan, mp2vg_scan_free);
     const int threads = d->cfg.num_threads > 0 ? d->cfg.num_threads : cpu_budget();
     // Parse workers: the thread budget less three (this feed loop, its gather helpers, the render
     // thread).  On the GPU box's 16-CPU quota (cgroup cpu.max on 256 CPUs) 15 workers of 16 threads
     // left some decode() calls throttled (c2 3,072 frames, device frames: 5.9k next to 9.7-10.3k
     // frames/s), 13 kept every call at 9.8-10.8k (profiles/r6/dropin_threads.jsonl).
-    int rc = parse_session_start(buf, len, &d->cfg, std::max(1, threads - 3), 4 * kChunk, &ps);
+    int rc = scan ? MP2VG_OK : parse_session_start(buf, len, &d->cfg, std::max(1, threads - 3), 4 * kChunk, &ps);
     t0 = trace_phase("dropin: headers", t0);
     if (rc != MP2VG_OK) return rc;
     std::unique_ptr<ParseSession, void (*)(ParseSession*)> guard(ps, parse_session_free);
-    d->hdrs = *parse_session_headers(ps);
-    const int32_t npics = parse_session_npics(ps);
-    const mp2vg_picture_t* pics = parse_session_pictures(ps);
-    std::vector<int32_t> display(parse_session_display(ps), parse_session_display(ps) + npics);
-    const int32_t* shard = parse_session_shards(ps);
+    d->hdrs = scan ? scan->hdrs : *parse_session_headers(ps);
+    const int32_t npics = scan ? (int32_t)scan->pics.size() : parse_session_npics(ps);
+    const mp2vg_picture_t* pics = scan ? scan->pics.data() : parse_session_pictures(ps);
+    const int32_t* disp = scan ? scan->display.data() : parse_session_display(ps);
+    std::vector<int32_t> display(disp, disp + npics);
+    const int32_t* shard = scan ? scan->shard.data() : parse_session_shards(ps);
     const int nl = (int)d->lanes.size();
     // Lanes take runs of whole shards, each run at least a chunk long: consecutive shards merge
     // until the run holds kChunk pictures, and run r goes to lane r % nl.  An I-only stream (one
@@ -560,6 +573,28 @@ static int decoder_decode(mp2vg_decoder_t* d, const uint8_t* buf, uint64_t len) 
         // chunk records with physical slots; MB and coefficient offsets local to the chunk,
         // gathered straight into pinned memory
         cp.assign(pics + s, pics + e);
+        if (scan) {
+            // the chunk's pictures with physical slots; the device writes their records itself
+            bool cross = false;
+            for (int i = 0; i < e - s; i++) {
+                mp2vg_picture_t& P = cp[i];
+                if (foreign(s + i, P.fwd_slot)) {
+                    cross = true;
+                    P.fwd_slot = -1;  // (a macroblock that does predict forward fails the upload's plan)
+                }
+                P.dst_slot = slot_of[P.dst_slot];
+                if (P.fwd_slot >= 0) P.fwd_slot = slot_of[P.fwd_slot];
+                if (P.bwd_slot >= 0) P.bwd_slot = slot_of[P.bwd_slot];
+                P.mb_first = (uint32_t)((uint64_t)i * mbs_per_pic);
+            }
+            tc = now_ms();
+            rc = mp2vg_batch_upload_es(L.ctx, scan, cp.data(), s, e - s);
+            if (rc == MP2VG_E_INVALID && cross) {
+                set_error("a B picture of a closed GOP predicts forward across GOPs: decode it on one device");
+                rc = MP2VG_E_UNSUPPORTED;
+            }
+            t_up += now_ms() - tc;
+        } else {
         tc = now_ms();
         size_t nc = 0;
         for (int p = s; p < e; p++) {
@@ -602,6 +637,7 @@ static int decoder_decode(mp2vg_decoder_t* d, const uint8_t* buf, uint64_t len) 
         tc = now_ms();
         rc = batch_upload_pinned(L.ctx, cp.data(), (int32_t)cp.size(), cm, nm, cc, nc);
         t_up += now_ms() - tc;
+        }
         tc = now_ms();
         if (rc == MP2VG_OK) rc = mp2vg_batch_decode(L.ctx);
         if (rc == MP2VG_OK && hipEventRecord(L.decoded, ctx_stream(L.ctx)) != hipSuccess) rc = MP2VG_E_HIP;

@@ -24,6 +24,7 @@
 #include <mutex>
 #include <vector>
 
+#include "scan.h"
 #include "syntax.h"
 
 namespace mp2vg {
@@ -585,13 +586,10 @@ struct ParseSession {
     }
 };
 
-int parse_session_start(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cfg, int threads, int window,
-                        ParseSession** out) {
-    if (!buf || !cfg || !out) return MP2VG_E_INVALID;
-    *out = nullptr;
-    if (mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
-    std::unique_ptr<ParseSession> S(new ParseSession());
-    Ctx& C = S->C;
+// Pass 1: start codes and headers -> C (geometry, per-picture headers, W, references, slices) and
+// res (picture records, GOP index, stream headers, shards, display order).  Shared by the parse
+// session and mp2vg_scan_es.
+static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cfg, Ctx& C, ParsedImpl* res) {
     C.buf = buf;
     C.len = len;
     C.width = cfg->width;
@@ -788,32 +786,6 @@ int parse_session_start(const uint8_t* buf, uint64_t len, const mp2vg_config_t* 
     tp = trace_phase("parse: headers", tp);
     const int npics = (int)C.pics.size();
     const size_t mbs_per_pic = (size_t)C.mbw * C.mbh;
-    S->mbs_per_pic = mbs_per_pic;
-    auto* res = new mp2vg_parsed();
-    S->res = res;
-    S->window = std::max(0, window);
-    if (S->window)
-        S->pic_mbs.assign(npics, nullptr);
-    else
-        res->mbs.resize(mbs_per_pic * npics);
-    for (auto& P : C.pics)
-        for (auto& j : P.slices) S->jobs.push_back(j);
-    S->outs.resize(S->jobs.size());
-    S->row_done.reset(new std::atomic<uint8_t>[(size_t)npics * C.mbh]);
-    for (size_t i = 0; i < (size_t)npics * C.mbh; i++) S->row_done[i].store(0, std::memory_order_relaxed);
-    S->slices_left.reset(new std::atomic<int>[npics]);
-    for (int p = 0; p < npics; p++) S->slices_left[p].store((int)C.pics[p].slices.size(), std::memory_order_relaxed);
-    S->pic_job_begin.assign(npics + 1, 0);
-    {
-        size_t j = 0;
-        for (int p = 0; p < npics; p++) {
-            S->pic_job_begin[p] = j;
-            j += C.pics[p].slices.size();
-        }
-        S->pic_job_begin[npics] = j;
-    }
-    S->status.assign(npics, 1);
-    S->err.assign(npics, std::string());
     // ---- picture records ----
     res->pics.resize(npics);
     for (int p = 0; p < npics; p++) {
@@ -865,6 +837,45 @@ int parse_session_start(const uint8_t* buf, uint64_t len, const mp2vg_config_t* 
         }
         if (held >= 0) res->display.push_back(held);
     }
+    return MP2VG_OK;
+}
+
+int parse_session_start(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cfg, int threads, int window,
+                        ParseSession** out) {
+    if (!buf || !cfg || !out) return MP2VG_E_INVALID;
+    *out = nullptr;
+    if (mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
+    std::unique_ptr<ParseSession> S(new ParseSession());
+    Ctx& C = S->C;
+    auto* res = new mp2vg_parsed();
+    S->res = res;
+    if (int rc = scan_pass1(buf, len, cfg, C, res)) return rc;
+    const int npics = (int)C.pics.size();
+    const size_t mbs_per_pic = (size_t)C.mbw * C.mbh;
+    S->mbs_per_pic = mbs_per_pic;
+    S->window = std::max(0, window);
+    if (S->window)
+        S->pic_mbs.assign(npics, nullptr);
+    else
+        res->mbs.resize(mbs_per_pic * npics);
+    for (auto& P : C.pics)
+        for (auto& j : P.slices) S->jobs.push_back(j);
+    S->outs.resize(S->jobs.size());
+    S->row_done.reset(new std::atomic<uint8_t>[(size_t)npics * C.mbh]);
+    for (size_t i = 0; i < (size_t)npics * C.mbh; i++) S->row_done[i].store(0, std::memory_order_relaxed);
+    S->slices_left.reset(new std::atomic<int>[npics]);
+    for (int p = 0; p < npics; p++) S->slices_left[p].store((int)C.pics[p].slices.size(), std::memory_order_relaxed);
+    S->pic_job_begin.assign(npics + 1, 0);
+    {
+        size_t j = 0;
+        for (int p = 0; p < npics; p++) {
+            S->pic_job_begin[p] = j;
+            j += C.pics[p].slices.size();
+        }
+        S->pic_job_begin[npics] = j;
+    }
+    S->status.assign(npics, 1);
+    S->err.assign(npics, std::string());
     int nthreads = threads > 0 ? threads : cpu_budget();
     nthreads = std::max(1, std::min(nthreads, std::max(1, (int)S->jobs.size())));
     ParseSession* sp = S.get();
@@ -1004,3 +1015,254 @@ extern "C" int mp2vg_parsed_shards(const mp2vg_parsed_t* p, int32_t* shard, int3
     return p->nshards;
 }
 extern "C" void mp2vg_parsed_free(mp2vg_parsed_t* p) { delete p; }
+
+// ---- host scan (pass 1 on its own) and the CPU twin of the device slice parser ---------------
+// mp2vg_scan_es keeps what a slice parser that runs elsewhere (parse.hip, one lane per slice)
+// needs: per picture the few header fields the macroblock syntax depends on, per slice its
+// picture, macroblock row and byte range.  The scan reads each slice's row itself and makes the
+// three row rejections of the host emitter, so every slice of the table owns its row: the
+// device needs no atomics.  mp2vg_scan_parse_host runs slice_parse.h, the kernels' source, on
+// the host with the kernels' buffer sizes.
+namespace mp2vg {
+
+void sp_tables(const uint32_t** words, size_t* nwords, SpTables* out) {
+    struct Built {
+        std::vector<uint32_t> w;
+        SpTables T{};
+    };
+    static const Built* built = [] {
+        Built* b = new Built();
+        const Tables& T = Tables::get();
+        auto put = [&](const std::vector<uint32_t>& v) {
+            const uint32_t at = (uint32_t)b->w.size();
+            b->w.insert(b->w.end(), v.begin(), v.end());
+            return at;
+        };
+        auto vals = [&](const vlc_code* c, int n) {
+            const uint32_t at = (uint32_t)b->w.size();
+            for (int i = 0; i < n; i++) b->w.push_back((uint32_t)c[i].a);
+            return at;
+        };
+        SpTables& S = b->T;
+        S.mba = put(T.mba.lut);
+        for (int p = 1; p <= 3; p++) S.mbtype[p] = put(T.mbtype[p].lut);
+        S.mbtype[0] = S.mbtype[1];
+        S.cbp = put(T.cbp.lut);
+        S.motion = put(T.motion_signed);
+        S.dc_luma = put(T.dc_luma.lut);
+        S.dc_chroma = put(T.dc_chroma.lut);
+        for (int t = 0; t < 2; t++) {
+            S.coef1[t] = put(T.coefs[t].l1);
+            S.coef2[t] = put(T.coefs[t].l2);
+        }
+        S.mba_val = vals(kMbaCodes, countof(kMbaCodes));
+        S.mbtype_val[1] = vals(kMbTypeI, countof(kMbTypeI));
+        S.mbtype_val[2] = vals(kMbTypeP, countof(kMbTypeP));
+        S.mbtype_val[3] = vals(kMbTypeB, countof(kMbTypeB));
+        S.mbtype_val[0] = S.mbtype_val[1];
+        S.cbp_val = vals(kCbpCodes, countof(kCbpCodes));
+        S.dc_luma_val = vals(kDcSizeLuma, countof(kDcSizeLuma));
+        S.dc_chroma_val = vals(kDcSizeChroma, countof(kDcSizeChroma));
+        S.rev6 = (uint32_t)b->w.size();
+        for (int i = 0; i < 64; i++) b->w.push_back(kRev6[i]);
+        S.w = b->w.data();
+        return b;
+    }();
+    if (words) *words = built->w.data();
+    if (nwords) *nwords = built->w.size();
+    if (out) *out = built->T;
+}
+
+void scan_span(const mp2vg_scan* s, int32_t first, int32_t npics, uint64_t* lo, uint64_t* hi) {
+    const uint32_t j0 = s->pic_slice[first], j1 = s->pic_slice[first + npics];
+    *lo = s->slices[j0].byte_off;
+    // up to the next picture's first slice (the headers between are what the host emitter's
+    // reader sees after the last slice too), or the end of the stream
+    *hi = (size_t)(first + npics) < s->pics.size() ? s->slices[j1].byte_off : s->len;
+}
+
+void sp_set_slice_error(int pic, uint64_t byte_off, int reason) {
+    char m[256];
+    snprintf(m, sizeof m, "picture %d slice @%llu: %s", pic, (unsigned long long)byte_off, sp_reason_text(reason));
+    set_error(m);
+}
+
+}  // namespace mp2vg
+
+extern "C" int mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cfg, mp2vg_scan_t** out) {
+    if (!out) return MP2VG_E_INVALID;
+    *out = nullptr;
+    if (!buf || !cfg) return MP2VG_E_INVALID;
+    if (mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
+    Ctx C;
+    ParsedImpl res;
+    if (int rc = scan_pass1(buf, len, cfg, C, &res)) return rc;
+    std::unique_ptr<mp2vg_scan> S(new mp2vg_scan());
+    S->buf = buf;
+    S->len = len;
+    S->cfg = *cfg;
+    SpGeom& g = S->g;
+    g.cf = C.g.cf;
+    g.nblocks = C.g.nblocks;
+    g.mbw = C.mbw;
+    g.mbh = C.mbh;
+    g.vext = C.vertical_size_value > 2800;
+    for (int i = 0; i < 3; i++) g.pw[i] = C.g.pw[i], g.ph[i] = C.g.ph[i];
+    g.mbw_c = C.g.mbw_c;
+    g.mbh_c = C.g.mbh_c;
+    S->pics = std::move(res.pics);
+    S->display = std::move(res.display);
+    S->gop = std::move(res.gop);
+    S->shard = std::move(res.shard);
+    S->nshards = res.nshards;
+    S->hdrs = res.hdrs;
+    const int npics = (int)C.pics.size();
+    std::vector<uint8_t> seen(C.mbh);
+    for (int p = 0; p < npics; p++) {
+        const PicWork& P = C.pics[p];
+        const PictureHdr& h = P.hdr;
+        SpPicHdr d{};
+        d.pct = (uint8_t)h.pct;
+        for (int s = 0; s < 2; s++)
+            for (int t = 0; t < 2; t++) d.f_code[s][t] = (uint8_t)h.f_code[s][t];
+        d.intra_dc_precision = (uint8_t)h.intra_dc_precision;
+        d.frame_pred_frame_dct = (uint8_t)h.frame_pred_frame_dct;
+        d.concealment_motion_vectors = (uint8_t)h.concealment_motion_vectors;
+        d.q_scale_type = (uint8_t)h.q_scale_type;
+        d.intra_vlc_format = (uint8_t)h.intra_vlc_format;
+        d.has_fwd = P.fwd >= 0;
+        d.has_bwd = P.bwd >= 0;
+        S->hdr.push_back(d);
+        S->pic_slice.push_back((uint32_t)S->slices.size());
+        std::fill(seen.begin(), seen.end(), 0);
+        for (const SliceJob& j : P.slices) {
+            // slice_vertical_position: the start code's last byte, extended by the 3 bits after it
+            // in pictures taller than 2800 lines (bytes past the buffer read as 0)
+            const int vpos = buf[j.byte_off + 3];
+            const int ext = g.vext && j.byte_off + 4 < len ? buf[j.byte_off + 4] >> 5 : 0;
+            const int row = (ext << 7) + vpos - 1;
+            if (row < 0 || row >= C.mbh) {
+                sp_set_slice_error(p, j.byte_off, SP_R_ROW_OUTSIDE);
+                return MP2VG_E_UNSUPPORTED;
+            }
+            if (seen[row]) {
+                sp_set_slice_error(p, j.byte_off, SP_R_TWO_SLICES);
+                return MP2VG_E_UNSUPPORTED;
+            }
+            seen[row] = 1;
+            S->slices.push_back({p, row, j.byte_off, j.byte_end});
+        }
+        for (int r = 0; r < C.mbh; r++)
+            if (!seen[r]) {
+                set_error(sp_reason_text(SP_R_ROW_UNCOVERED));
+                return MP2VG_E_UNSUPPORTED;
+            }
+    }
+    S->pic_slice.push_back((uint32_t)S->slices.size());
+    *out = S.release();
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_scan_counts(const mp2vg_scan_t* s, int32_t* npics, uint64_t* nslices) {
+    if (!s) return MP2VG_E_INVALID;
+    if (npics) *npics = (int32_t)s->pics.size();
+    if (nslices) *nslices = s->slices.size();
+    return MP2VG_OK;
+}
+extern "C" const mp2vg_picture_t* mp2vg_scan_pictures(const mp2vg_scan_t* s) { return s ? s->pics.data() : nullptr; }
+extern "C" int mp2vg_scan_display_order(const mp2vg_scan_t* s, int32_t* order, int32_t n) {
+    if (!s || !order || n < (int32_t)s->display.size()) return MP2VG_E_INVALID;
+    if (!s->display.empty()) memcpy(order, s->display.data(), s->display.size() * 4);
+    return (int)s->display.size();
+}
+extern "C" int mp2vg_scan_gop_index(const mp2vg_scan_t* s, int32_t* gop, int32_t n) {
+    if (!s || !gop || n < (int32_t)s->gop.size()) return MP2VG_E_INVALID;
+    if (!s->gop.empty()) memcpy(gop, s->gop.data(), s->gop.size() * 4);
+    return (int)s->gop.size();
+}
+extern "C" int mp2vg_scan_shards(const mp2vg_scan_t* s, int32_t* shard, int32_t n) {
+    if (!s || !shard || n < (int32_t)s->shard.size()) return MP2VG_E_INVALID;
+    if (!s->shard.empty()) memcpy(shard, s->shard.data(), s->shard.size() * 4);
+    return s->nshards;
+}
+extern "C" int mp2vg_scan_stream_headers(const mp2vg_scan_t* s, mp2vg_stream_headers_t* out) {
+    if (!s || !out) return MP2VG_E_INVALID;
+    *out = s->hdrs;
+    return MP2VG_OK;
+}
+extern "C" void mp2vg_scan_free(mp2vg_scan_t* s) { delete s; }
+
+extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32_t npics, mp2vg_mb_t* mbs,
+                                     uint64_t nmbs, uint32_t* coefs, uint64_t ncoefs, uint64_t* nmbs_out,
+                                     uint64_t* ncoefs_out) {
+    if (!s || first < 0 || npics <= 0 || (uint64_t)first + (uint64_t)npics > s->pics.size()) return MP2VG_E_INVALID;
+    const SpGeom& g = s->g;
+    const uint64_t per_pic = (uint64_t)g.mbw * g.mbh;
+    if (mbs && nmbs != per_pic * npics) {
+        set_error("mp2vg_scan_parse_host: nmbs is not the range's macroblock count");
+        return MP2VG_E_INVALID;
+    }
+    if (coefs && !mbs) return MP2VG_E_INVALID;
+    SpTables T;
+    sp_tables(nullptr, nullptr, &T);
+    // the span the device gets, in a buffer of the device's size: the bytes, then kSpanPad zeros
+    uint64_t lo, hi;
+    scan_span(s, first, npics, &lo, &hi);
+    const uint64_t span = hi - lo;
+    uint8_t* bs = (uint8_t*)malloc(span + kSpanPad);
+    if (!bs) return MP2VG_E_NOMEM;
+    memcpy(bs, s->buf + lo, span);
+    memset(bs + span, 0, kSpanPad);
+    struct Free {
+        uint8_t* p;
+        ~Free() { free(p); }
+    } guard{bs};
+    const uint32_t j0 = s->pic_slice[first], j1 = s->pic_slice[first + npics];
+    std::vector<SpResult> res(j1 - j0);
+    auto row_of = [&](const SpSlice& sl) { return mbs + per_pic * (sl.pic - first) + (uint64_t)sl.mb_row * g.mbw; };
+    for (uint32_t j = j0; j < j1; j++) {  // count pass
+        const SpSlice& sl = s->slices[j];
+        const SpPicHdr& h = s->hdr[sl.pic];
+        if (mbs)
+            sp_parse_slice(T, g, h, bs, (int64_t)(sl.byte_off - lo), (int64_t)(sl.byte_end - lo), (int64_t)span,
+                           sl.mb_row, SpCountOut{row_of(sl)}, res[j - j0]);
+        else
+            sp_parse_slice(T, g, h, bs, (int64_t)(sl.byte_off - lo), (int64_t)(sl.byte_end - lo), (int64_t)span,
+                           sl.mb_row, SpNullOut{}, res[j - j0]);
+        if (res[j - j0].iters > sp_iter_bound(sl.byte_end - sl.byte_off, g.mbw)) {
+            set_error("mp2vg_scan_parse_host: iteration bound exceeded");
+            return MP2VG_E_STATE;
+        }
+    }
+    for (uint32_t j = j0; j < j1; j++)  // the first failing slice in stream order
+        if (res[j - j0].status != MP2VG_OK) {
+            sp_set_slice_error(s->slices[j].pic, s->slices[j].byte_off, res[j - j0].reason);
+            return res[j - j0].status;
+        }
+    std::vector<uint64_t> base(j1 - j0 + 1, 0);  // scan: exclusive prefix sum in table order
+    for (uint32_t j = j0; j < j1; j++) base[j - j0 + 1] = base[j - j0] + res[j - j0].ncoef;
+    const uint64_t total = base[j1 - j0];
+    if (nmbs_out) *nmbs_out = per_pic * npics;
+    if (ncoefs_out) *ncoefs_out = total;
+    if (total >= (1ull << 32)) {
+        set_error("batch too large");
+        return MP2VG_E_INVALID;
+    }
+    if (!mbs) return MP2VG_OK;  // the counts call
+    if (ncoefs != total || (total && !coefs)) {
+        set_error("mp2vg_scan_parse_host: ncoefs is not the counted number of words");
+        return MP2VG_E_INVALID;
+    }
+    for (uint32_t j = j0; j < j1; j++) {  // emit pass
+        const SpSlice& sl = s->slices[j];
+        SpResult r2;
+        const SpEmitOut eo{row_of(sl), coefs + base[j - j0], res[j - j0].ncoef, (uint32_t)base[j - j0]};
+        sp_parse_slice(T, g, s->hdr[sl.pic], bs, (int64_t)(sl.byte_off - lo), (int64_t)(sl.byte_end - lo), (int64_t)span,
+                       sl.mb_row, eo, r2);
+        if (r2.status != MP2VG_OK || r2.ncoef != res[j - j0].ncoef) {
+            set_error("mp2vg_scan_parse_host: the emit pass differs from the count pass");
+            return MP2VG_E_STATE;
+        }
+    }
+    return MP2VG_OK;
+}

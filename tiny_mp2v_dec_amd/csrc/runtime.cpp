@@ -18,6 +18,7 @@
 
 #include "export_kernel.h"
 #include "hipchk.h"
+#include "parse_kernel.h"
 #include "recon_kernel.h"
 #include "syntax.h"
 #include "tensor_kernel.h"
@@ -123,6 +124,7 @@ struct Bank {
     std::vector<std::vector<int32_t>> foot;  // per picture set: the slots it writes or reads
     TilePlan tiles;
     int32_t npics = 0;
+    uint64_t nmbs = 0, ncoefs = 0;  // records of the resident batch (mp2vg_batch_record_counts)
     hipEvent_t uploaded = nullptr;  // on ustream, after the bank's copies
     hipEvent_t consumed = nullptr;  // on stream, after the last decode that read the bank
     bool decoded = false;           // `consumed` has been recorded
@@ -203,6 +205,11 @@ struct mp2vg_ctx {
     // when the main stream was last synchronised.  Callers that never export never wait.
     std::vector<uint32_t> swaited;
     uint32_t export_synced = 0;
+
+    // the device parse's own state (parse_dev.cpp: bitstream, tables, per-slice results, events),
+    // created at the first mp2vg_batch_upload_es and freed by es_free at destroy
+    void* es = nullptr;
+    void (*es_free)(void*) = nullptr;
 };
 
 template <class T>
@@ -304,6 +311,7 @@ extern "C" int mp2vg_destroy(mp2vg_ctx_t* c) {
     hipSetDevice(c->cfg.device);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->ustream) hipStreamSynchronize(c->ustream);
+    if (c->es && c->es_free) c->es_free(c->es);
     for (auto& h : c->hist) {
         for (auto e : h.l) hipEventDestroy(e);
         for (auto e : h.s)
@@ -526,6 +534,10 @@ extern "C" int mp2vg_reserve_slots(mp2vg_ctx_t* c, int32_t nslots) {
     return finish_reserve(c, nslots);
 }
 
+static int plan_from_uses(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics, const uint8_t* uses_of,
+                          const char* const* err, std::vector<SliceDesc>& slices, std::vector<Launch>& launches,
+                          std::vector<std::vector<int32_t>>* foot, TilePlan* tplan);
+
 // Validate the batch so no kernel access can leave its buffers, and compute dependency levels.
 static int plan_batch(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics, const mp2vg_mb_t* mbs,
                       uint64_t nmbs, const uint32_t* coefs, uint64_t ncoefs, std::vector<SliceDesc>& slices,
@@ -538,9 +550,6 @@ static int plan_batch(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics
         set_error("batch with 2^30 or more coefficient words (4 GB): split it");
         return MP2VG_E_INVALID;
     }
-    std::vector<int> level(npics, 0);
-    std::vector<int> last_write(c->nslots, -1), max_read(c->nslots, -1);
-    int maxlevel = -1;
     // per-picture record validation (O(MBs + coefficient words)) runs on host threads; the first
     // failing picture in batch order reports its error
     std::vector<uint8_t> uses_of(2 * (size_t)npics, 0);
@@ -642,9 +651,23 @@ static int plan_batch(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics
         return nullptr;
     };
     parallel_for(npics, 16, [&](int p) { err[p] = validate(p); });
+    return plan_from_uses(c, pics, npics, uses_of.data(), err.data(), slices, launches, foot, tplan);
+}
+
+// The plan proper: dependency levels, picture sets, anchor tiles, slices and launches, from the
+// picture records and which references each picture's macroblocks use (uses_of[2 p], [2 p + 1]:
+// forward, backward), however those were found (plan_batch's record scan, or the device parse's
+// count pass).  err[p] (err may be null) is picture p's record error, reported in batch order.
+static int plan_from_uses(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics, const uint8_t* uses_of,
+                          const char* const* err, std::vector<SliceDesc>& slices, std::vector<Launch>& launches,
+                          std::vector<std::vector<int32_t>>* foot, TilePlan* tplan) {
+    const int mbw = c->cfg.width / 16, mbh = c->cfg.height / 16;
+    std::vector<int> level(npics, 0);
+    std::vector<int> last_write(c->nslots, -1), max_read(c->nslots, -1);
+    int maxlevel = -1;
     for (int p = 0; p < npics; p++) {
         const mp2vg_picture_t& P = pics[p];
-        if (err[p]) {
+        if (err && err[p]) {
             set_error(err[p]);
             return MP2VG_E_INVALID;
         }
@@ -994,8 +1017,128 @@ static int batch_upload(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npi
     b.post_of = std::move(post_of);
     b.tiles = std::move(tplan);
     b.npics = npics;
+    b.nmbs = nmbs;
+    b.ncoefs = ncoefs;
     c->cur = k;
     c->batch_ready = true;
+    return MP2VG_OK;
+}
+
+// ---- the context's side of the device parse (parse_dev.cpp: mp2vg_batch_upload_es) -----------
+namespace mp2vg {
+// Picture-level checks (what plan_batch checks before it reads a record), then the next bank with
+// room for the batch's pictures and MB records; the previous decode that read the bank is waited
+// for.  No batch is resident from here until es_commit.
+int es_begin(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics, uint64_t nmbs, EsBank* out) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    c->batch_ready = false;
+    const int mbw = c->cfg.width / 16, mbh = c->cfg.height / 16;
+    for (int p = 0; p < npics; p++) {
+        const mp2vg_picture_t& P = pics[p];
+        const char* e = nullptr;
+        if (P.picture_coding_type < 1 || P.picture_coding_type > 3) e = "picture_coding_type is not 1 (I), 2 (P) or 3 (B)";
+        else if (P.mb_width != mbw || P.mb_height != mbh) e = "picture size differs from the context geometry";
+        else if (P.dst_slot < 0 || P.dst_slot >= c->nslots || P.fwd_slot >= c->nslots || P.bwd_slot >= c->nslots)
+            e = "frame slot out of range (mp2vg_reserve_slots)";
+        else if ((uint64_t)P.mb_first + (uint64_t)mbw * mbh > nmbs) e = "picture MB range outside the batch";
+        if (e) {
+            set_error(e);
+            return MP2VG_E_INVALID;
+        }
+    }
+    Bank& b = c->bank[(c->cur + 1) & 1];
+    if (b.decoded) HIPCHK(hipEventSynchronize(b.consumed));
+    int rc;
+    if ((rc = grow(b.d_pics, b.cap_pics, (size_t)npics)) != MP2VG_OK) return rc;
+    if ((rc = grow(b.d_mbs, b.cap_mbs, (size_t)nmbs + kMbPad)) != MP2VG_OK) return rc;
+    out->device = c->cfg.device;
+    out->stream = c->ustream;
+    out->d_mbs = b.d_mbs;
+    out->state = &c->es;
+    out->state_free = &c->es_free;
+    return MP2VG_OK;
+}
+// the bank's coefficient array for ncoefs words (plus the kernels' prefetch pad)
+int es_coefs(mp2vg_ctx_t* c, uint64_t ncoefs, uint32_t** d_coefs) {
+    if (ncoefs + kCoefPad >= (1ull << 30)) {
+        set_error("batch with 2^30 or more coefficient words (4 GB): split it");
+        return MP2VG_E_INVALID;
+    }
+    Bank& b = c->bank[(c->cur + 1) & 1];
+    const int rc = grow(b.d_coefs, b.cap_coefs, (size_t)ncoefs + kCoefPad);
+    *d_coefs = b.d_coefs;
+    return rc;
+}
+// Plan the batch from the count pass's reference usage (the trusted route: the device parser's
+// records meet the contract by construction), send the small arrays and make the batch resident.
+// The caller has enqueued the emit pass on the bank's stream.
+int es_commit(mp2vg_ctx_t* c, const mp2vg_picture_t* pics, int32_t npics, uint64_t nmbs, uint64_t ncoefs,
+              const uint8_t* uses_of) {
+    std::vector<SliceDesc> slices;
+    std::vector<Launch> lb;
+    std::vector<std::vector<int32_t>> foot;
+    TilePlan tplan;
+    int rc = plan_from_uses(c, pics, npics, uses_of, nullptr, slices, lb, &foot, &tplan);
+    if (rc != MP2VG_OK) return rc;
+    const int k = (c->cur + 1) & 1;
+    Bank& b = c->bank[k];
+    if ((rc = grow(b.d_slices, b.cap_slices, slices.size())) != MP2VG_OK) return rc;
+    std::vector<int32_t> ps;
+    std::vector<std::pair<int32_t, int32_t>> post_of(lb.size(), {0, 0});
+    for (size_t i = 0; i < lb.size(); i++) {
+        post_of[i].first = (int32_t)ps.size();
+        for (const auto& pc : tplan.post)
+            if (pc.first == (int32_t)i) ps.push_back(pc.second);
+        post_of[i].second = (int32_t)ps.size();
+    }
+    if (!ps.empty() && (rc = grow(b.d_post, b.cap_post, ps.size())) != MP2VG_OK) return rc;
+    if ((rc = upload(c, b.d_pics, pics, sizeof(mp2vg_picture_t) * npics, false)) != MP2VG_OK) return rc;
+    if ((rc = upload(c, b.d_slices, slices.data(), sizeof(SliceDesc) * slices.size(), false)) != MP2VG_OK) return rc;
+    if (!ps.empty() && (rc = upload(c, b.d_post, ps.data(), sizeof(int32_t) * ps.size(), false)) != MP2VG_OK) return rc;
+    HIPCHK(hipEventRecord(b.uploaded, c->ustream));
+    HIPCHK(hipStreamSynchronize(c->ustream));
+    b.launches = std::move(lb);
+    b.foot = std::move(foot);
+    b.post_of = std::move(post_of);
+    b.tiles = std::move(tplan);
+    b.npics = npics;
+    b.nmbs = nmbs;
+    b.ncoefs = ncoefs;
+    c->cur = k;
+    c->batch_ready = true;
+    return MP2VG_OK;
+}
+void* ctx_es_state(mp2vg_ctx_t* c) { return c->es; }
+const mp2vg_config_t* ctx_config(const mp2vg_ctx_t* c) { return &c->cfg; }
+}  // namespace mp2vg
+
+extern "C" int mp2vg_batch_record_counts(mp2vg_ctx_t* c, uint64_t* nmbs, uint64_t* ncoefs) {
+    if (!c) return MP2VG_E_INVALID;
+    if (!c->batch_ready) {
+        set_error("no batch uploaded");
+        return MP2VG_E_STATE;
+    }
+    if (nmbs) *nmbs = c->bank[c->cur].nmbs;
+    if (ncoefs) *ncoefs = c->bank[c->cur].ncoefs;
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_batch_download_records(mp2vg_ctx_t* c, mp2vg_mb_t* mbs, uint64_t nmbs, uint32_t* coefs,
+                                            uint64_t ncoefs) {
+    if (!c || !mbs || (!coefs && ncoefs)) return MP2VG_E_INVALID;
+    if (!c->batch_ready) {
+        set_error("no batch uploaded");
+        return MP2VG_E_STATE;
+    }
+    const Bank& b = c->bank[c->cur];
+    if (nmbs != b.nmbs || ncoefs != b.ncoefs) {
+        set_error("record array sizes differ from the resident batch (mp2vg_batch_record_counts)");
+        return MP2VG_E_INVALID;
+    }
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipEventSynchronize(b.uploaded));
+    HIPCHK(hipMemcpy(mbs, b.d_mbs, sizeof(mp2vg_mb_t) * nmbs, hipMemcpyDeviceToHost));
+    if (ncoefs) HIPCHK(hipMemcpy(coefs, b.d_coefs, sizeof(uint32_t) * ncoefs, hipMemcpyDeviceToHost));
     return MP2VG_OK;
 }
 

@@ -20,6 +20,11 @@ reference's public members do (decoder.h:124-130).
 decoder_config_t(device_frames=True) opts into the device-pointer output path
 (MP2VG_DECODER_DEVICE_FRAMES): frames stay in HBM (no PCIe download), frame_c.device_ptr(i) gives
 the plane's device address and get_planes(i) copies the plane to the host on demand.
+
+decoder_config_t(device_parse=True) opts into parsing the slices on the device
+(MP2VG_DECODER_DEVICE_PARSE): decode() only scans the stream on the host and no parse workers
+start; frames, order and lanes are the same.  Measured slower than the host parse at the decoder's
+16-picture chunks (profiles/device_parse/README.md): off by default.
 """
 import ctypes
 from dataclasses import dataclass
@@ -41,9 +46,11 @@ class decoder_config_t:  # noqa: N801  (reference name)
     device: int = 0
     device_frames: bool = False
     devices: list = None  # GOP sharding over these devices (None: [device])
+    device_parse: bool = False  # MP2VG_DECODER_DEVICE_PARSE: slices parsed on the device, no parse workers
 
 
 MP2VG_DECODER_DEVICE_FRAMES = 1  # include/mp2vg.h
+MP2VG_DECODER_DEVICE_PARSE = 4
 _hip = None
 
 
@@ -141,7 +148,8 @@ class mp2v_decoder_c:  # noqa: N801  (reference name)
         self._cfg = _lib.make_config(config.width, config.height, config.chroma_format, config.pictures_pool_size,
                                      config.num_threads, config.reordering, config.device)
         self._device = bool(config.device_frames)
-        self._cfg.reserved = MP2VG_DECODER_DEVICE_FRAMES if self._device else 0
+        self._cfg.reserved = ((MP2VG_DECODER_DEVICE_FRAMES if self._device else 0) |
+                              (MP2VG_DECODER_DEVICE_PARSE if config.device_parse else 0))
         self._error = None
 
         def _cb(user, fptr):

@@ -83,6 +83,72 @@ class Parsed:
         return len(self.pics)
 
 
+class Scan:
+    """Host scan of an elementary stream (mp2vg_scan_es): what Parsed holds except the MB records
+    and coefficient words, which DeviceContext.upload_es has the device parse from the bitstream
+    (parse_host: the same parser on the CPU).  Keeps the stream's bytes alive."""
+
+    def __init__(self, es: bytes, width, height, chroma_format, reordering=True):
+        self.width, self.height, self.chroma_format = width, height, chroma_format
+        cfg = _lib.make_config(width, height, chroma_format, reordering=reordering)
+        self._buf = np.frombuffer(es, dtype=np.uint8)
+        self.h = ctypes.c_void_p()
+        check(lib().mp2vg_scan_es(self._buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
+                                  ctypes.byref(self.h)), "scan_es")
+        npics, nslices = ctypes.c_int32(), ctypes.c_uint64()
+        lib().mp2vg_scan_counts(self.h, ctypes.byref(npics), ctypes.byref(nslices))
+        n, self.nslices = npics.value, nslices.value
+        self.pics = _copy_out(lib().mp2vg_scan_pictures(self.h), n * 288, PIC_DTYPE)
+        order = (ctypes.c_int32 * max(n, 1))()
+        lib().mp2vg_scan_display_order(self.h, order, n)
+        self.display = np.array(order[:n], dtype=np.int32)
+        gop = (ctypes.c_int32 * max(n, 1))()
+        lib().mp2vg_scan_gop_index(self.h, gop, n)
+        self.gop = np.array(gop[:n], dtype=np.int32)
+        shard = (ctypes.c_int32 * max(n, 1))()
+        self.nshards = check_count(lib().mp2vg_scan_shards(self.h, shard, n), "scan_shards")
+        self.shard = np.array(shard[:n], dtype=np.int32)
+        self.headers = _lib.StreamHeaders()
+        check(lib().mp2vg_scan_stream_headers(self.h, ctypes.byref(self.headers)), "scan_stream_headers")
+
+    @property
+    def npics(self):
+        return len(self.pics)
+
+    def parse_host(self, first=0, npics=None):
+        """(mbs, coefs) of pictures [first, first + npics) from the CPU twin of the device parse
+        (mp2vg_scan_parse_host): a counts call, then arrays of exactly the counted sizes."""
+        npics = self.npics - first if npics is None else npics
+        if npics == 0:  # (a stream without pictures scans, as it parses: nothing to do)
+            return np.zeros(0, MB_DTYPE), np.zeros(0, np.uint32)
+        nm, nc = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().mp2vg_scan_parse_host(self.h, first, npics, None, 0, None, 0, ctypes.byref(nm), ctypes.byref(nc)),
+              "scan_parse_host")
+        mbs, coefs = np.zeros(nm.value, MB_DTYPE), np.zeros(nc.value, np.uint32)
+        vp = ctypes.c_void_p
+        check(lib().mp2vg_scan_parse_host(self.h, first, npics, mbs.ctypes.data_as(vp), len(mbs),
+                                          coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs), None, None),
+              "scan_parse_host")
+        return mbs, coefs
+
+    def close(self):
+        if self.h:
+            lib().mp2vg_scan_free(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def plan_batch(width, height, chroma_format, nslots, pics, mbs, coefs, one_stream=False):
     """mp2vg_batch_validate: the upload's host-side record validation and launch planning, with no
     device.  Returns (launch index of each picture, kernel mode of each launch: 0 I, 1 P, 2 B,
@@ -150,6 +216,36 @@ class DeviceContext:
         vp = ctypes.c_void_p
         check(lib().mp2vg_batch_upload(self.h, pics.ctypes.data_as(vp), len(pics), mbs.ctypes.data_as(vp), len(mbs),
                                        coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs)), "batch_upload")
+
+    def upload_es(self, scan, first=0, npics=None, pics=None):
+        """Pictures [first, first + npics) of a Scan as the resident batch, their slices parsed on
+        the device (mp2vg_batch_upload_es).  pics: the range's picture records with the caller's
+        slots and mb_first (default: the scan's, mb_first rebased to the range)."""
+        npics = scan.npics - first if npics is None else npics
+        ptr = None
+        if pics is not None:
+            pics = np.ascontiguousarray(pics, PIC_DTYPE)
+            if len(pics) != npics:
+                raise ValueError("pics must hold one record per picture of the range")
+            ptr = pics.ctypes.data_as(ctypes.c_void_p)
+        check(lib().mp2vg_batch_upload_es(self.h, scan.h, ptr, int(first), int(npics)), "batch_upload_es")
+
+    def download_records(self):
+        """(mbs, coefs) of the resident batch, copied from HBM (mp2vg_batch_download_records)."""
+        nm, nc = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().mp2vg_batch_record_counts(self.h, ctypes.byref(nm), ctypes.byref(nc)), "batch_record_counts")
+        mbs, coefs = np.zeros(nm.value, MB_DTYPE), np.zeros(nc.value, np.uint32)
+        vp = ctypes.c_void_p
+        check(lib().mp2vg_batch_download_records(self.h, mbs.ctypes.data_as(vp), len(mbs),
+                                                 coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs)),
+              "batch_download_records")
+        return mbs, coefs
+
+    def parse_times_ms(self):
+        """Device ms of the last upload_es: [count pass, scan, emit pass] (mp2vg_last_parse_times)."""
+        ms = (ctypes.c_float * 3)()
+        check(lib().mp2vg_last_parse_times(self.h, ms), "last_parse_times")
+        return list(ms)
 
     def decode(self):
         check(lib().mp2vg_batch_decode(self.h), "batch_decode")
@@ -294,14 +390,17 @@ def export_matrix(headers):
     return m.value
 
 
-def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0):
+def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0,
+               device_parse=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one torch.uint8 RGB tensor on cuda:<device>, cropped to the sequence header's
     horizontal_size_value x vertical_size_value when these are set and no larger than the coded
     size.  matrix=None takes the stream's matrix_coefficients (export_matrix).  The stream is one
     batch in a context of as many slots as it has pictures; a stream without pictures gives an
-    empty tensor, and one of more than 65535 pictures is exported in several calls."""
-    parsed = Parsed(es, width, height, chroma_format)
+    empty tensor, and one of more than 65535 pictures is exported in several calls.
+    device_parse=True scans the stream on the host and parses its slices on the device (Scan,
+    DeviceContext.upload_es) instead of uploading host-parsed records; the result is the same."""
+    parsed = (Scan if device_parse else Parsed)(es, width, height, chroma_format)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     size = (w, h) if 0 < w <= width and 0 < h <= height else None
@@ -312,7 +411,10 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
     if not parsed.npics:
         return out
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
-        ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        if device_parse:
+            ctx.upload_es(parsed)
+        else:
+            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
         ctx.decode()
         for i in range(0, parsed.npics, EXPORT_MAX_FRAMES):  # mp2vg_export_slots takes 65535 per call
             part = parsed.display[i:i + EXPORT_MAX_FRAMES]
@@ -323,15 +425,15 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
 
 
 def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
-                  layout="nchw", chroma="linear", matrix=None, device=0):
+                  layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
     dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
     horizontal_size_value x vertical_size_value at the top left when these are set and no larger
     than the coded size, else the coded frame; matrix=None takes the stream's matrix_coefficients.
     A stream without pictures gives an empty tensor, and one of more than 65535 pictures is
-    exported in several calls."""
-    parsed = Parsed(es, width, height, chroma_format)
+    exported in several calls.  device_parse as in decode_rgb."""
+    parsed = (Scan if device_parse else Parsed)(es, width, height, chroma_format)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     if crop is None and 0 < w <= width and 0 < h <= height:
@@ -343,7 +445,10 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     if not parsed.npics:
         return out
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
-        ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        if device_parse:
+            ctx.upload_es(parsed)
+        else:
+            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
         ctx.decode()
         for i in range(0, parsed.npics, EXPORT_MAX_FRAMES):  # mp2vg_tensor_slots takes 65535 per call
             part = parsed.display[i:i + EXPORT_MAX_FRAMES]
