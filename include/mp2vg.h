@@ -265,8 +265,9 @@ int  mp2vg_slot_digests(mp2vg_ctx_t* ctx, const int32_t* slots, int32_t n, uint6
  *              j1 = j = y, wv0, wv1 = 4, 0;  4:2:0 / 4:2:2: k = x >> 1, k1 = k (x even) or k + 1
  *              (x odd); 4:4:4: k1 = k = x.  j1 and k1 clamp to the coded chroma plane, not to the
  *              exported rectangle: a crop filters with the real neighbouring samples.
- * Interlaced (field) chroma siting is out of scope: field pictures' chroma is filtered as if the
- * frame were progressive. */
+ * The RGB export has no field mode: chroma is filtered as if the frame were progressive.  The
+ * full-resolution deinterlaced (or field-sited) RGB image of an interlaced frame is an identity-size
+ * U8 tensor export (out == src, Q = 64 P) with a MP2VG_FIELD_* mode, below. */
 enum { MP2VG_EXPORT_RGB_PLANAR = 0 /* [n][3][h][w] */, MP2VG_EXPORT_RGB_PACKED = 1 /* [n][h][w][3] */ };
 enum { MP2VG_EXPORT_CHROMA_NEAREST = 0, MP2VG_EXPORT_CHROMA_LINEAR = 1 };
 typedef struct mp2vg_export {
@@ -340,8 +341,36 @@ int  mp2vg_export_planes(int32_t device, const uint8_t* const planes[3], const i
  *    -mean / std.
  * 5. Layout: planar [n][3][out_h][out_w] or packed [n][out_h][out_w][3] (MP2VG_EXPORT_RGB_*),
  *    tight; dst is aligned to the element size and no more.
- * Out of scope: interlaced chroma siting (as above), filters other than the triangle, padding. */
+ *
+ * Field modes (mp2vg_tensor_slots_fields / mp2vg_tensor_planes_field), for frame pictures whose two
+ * fields are 1/50 or 1/60 s apart (progressive_frame = 0: mp2vg_parsed_picture_flags).  A mode
+ * replaces step 1 only: the rectangle, the tap tables (those of the unchanged rectangle, so the
+ * output geometry is the same in every mode and a single field stays spatially aligned with the
+ * frame), both passes, the normalisation and the layout are untouched.  H = the coded height;
+ * L_p[y] = line y converted with the matrix arithmetic above and the FIELD CHROMA of parity
+ * p = y & 1:
+ *     4:2:2, 4:4:4: the progressive chroma of line y (no vertical subsampling).
+ *     4:2:0: j = 2 (y >> 2) + (y & 1), the chroma row of the same field; k, k1 as in the RGB export.
+ *         NEAREST: C[j][k]
+ *         LINEAR:  (wv0 (C[j][k] + C[j][k1]) + wv1 (C[j1][k] + C[j1][k1]) + 8) >> 4, one rounding,
+ *                  y mod 4 = 0: j1 = j - 2, wv0, wv1 = 7, 1      1: j1 = j - 2, 5, 3
+ *                            2: j1 = j + 2, 5, 3                 3: j1 = j + 2, 7, 1
+ *                  (the 1/4 and 3/4 line siting of interlaced 4:2:0); a j1 outside 0 .. ch - 1
+ *                  becomes j, so it never leaves the field.
+ *     (The progressive rule (3 A + B + 4) >> 3 equals (6 A + 2 B + 8) >> 4 exactly.)
+ * MP2VG_FIELD_PROGRESSIVE: P as defined in step 1.
+ * MP2VG_FIELD_WEAVE:  P[y] = L_{y & 1}[y]: both fields, each line with its own field's chroma
+ *     (4:2:2 and 4:4:4: equal to PROGRESSIVE bit for bit).
+ * MP2VG_FIELD_TOP (p = 0) / MP2VG_FIELD_BOTTOM (p = 1): P[y] = L_p[y] on lines of parity p; a line
+ *     of the other parity is the rounded average per channel (L_p[a] + L_p[b] + 1) >> 1 of the 8-bit
+ *     lines a = y - 1, b = y + 1; a < 0 becomes b and b > H - 1 becomes a (row 0 of BOTTOM is line 1,
+ *     row H - 1 of TOP is line H - 2).  a and b are lines of the coded frame, not clamped to the
+ *     rectangle (the rule of the chroma taps).
+ * A mode other than PROGRESSIVE needs an even coded height, a multiple of 4 for 4:2:0 (every decoder
+ * context has one), else MP2VG_E_INVALID.
+ * Out of scope: motion-adaptive deinterlacing, filters other than the triangle, padding. */
 enum { MP2VG_TENSOR_U8 = 0, MP2VG_TENSOR_F16 = 1, MP2VG_TENSOR_BF16 = 2, MP2VG_TENSOR_F32 = 3 };
+enum { MP2VG_FIELD_PROGRESSIVE = 0, MP2VG_FIELD_TOP = 1, MP2VG_FIELD_BOTTOM = 2, MP2VG_FIELD_WEAVE = 3 };
 #define MP2VG_TENSOR_MAX_TAPS 65
 typedef struct mp2vg_tensor {
     int32_t layout, matrix, chroma; /* as mp2vg_export_t */
@@ -377,6 +406,18 @@ int  mp2vg_tensor_slots(mp2vg_ctx_t* ctx, const int32_t* slots, int32_t n, const
 int  mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
                          int32_t chroma_format, int32_t coded_w, int32_t coded_h, const mp2vg_tensor_t* t,
                          void* dst_device, uint64_t dst_bytes);
+/* mp2vg_tensor_slots with a field mode per frame of the launch: frame i is slot slots[i] in mode
+ * fields[i] (MP2VG_FIELD_*; fields = NULL: all PROGRESSIVE, which is mp2vg_tensor_slots bit for
+ * bit).  Both fields of each picture in temporal order is one launch with every slot listed twice.
+ * Ordering, staging and limits as mp2vg_tensor_slots; the field list is copied with the slot list
+ * before the call returns.  A field value outside 0..3 is MP2VG_E_INVALID, nothing written; every
+ * argument is checked before the first HIP call. */
+int  mp2vg_tensor_slots_fields(mp2vg_ctx_t* ctx, const int32_t* slots, const int32_t* fields, int32_t n,
+                               const mp2vg_tensor_t* t, void* dst_device, uint64_t dst_bytes);
+/* mp2vg_tensor_planes in one field mode (field = MP2VG_FIELD_PROGRESSIVE: mp2vg_tensor_planes). */
+int  mp2vg_tensor_planes_field(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                               int32_t chroma_format, int32_t coded_w, int32_t coded_h, int32_t field,
+                               const mp2vg_tensor_t* t, void* dst_device, uint64_t dst_bytes);
 
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c
@@ -444,6 +485,12 @@ const uint32_t*        mp2vg_parsed_coefs(const mp2vg_parsed_t* p);
 int  mp2vg_parsed_display_order(const mp2vg_parsed_t* p, int32_t* order, int32_t n);
 /* GOP index (0-based, by group_start_code) of each picture, for GOP sharding */
 int  mp2vg_parsed_gop_index(const mp2vg_parsed_t* p, int32_t* gop, int32_t n);
+/* interlace flags of each picture (decode order), from its picture_coding_extension: which
+ * pictures hold two fields 1/50 or 1/60 s apart (progressive_frame = 0) and which field is the
+ * earlier one: what a caller needs to pick the MP2VG_FIELD_* mode of a tensor export.  Returns the
+ * number of pictures. */
+enum { MP2VG_PIC_PROGRESSIVE_FRAME = 1, MP2VG_PIC_TOP_FIELD_FIRST = 2, MP2VG_PIC_REPEAT_FIRST_FIELD = 4 };
+int  mp2vg_parsed_picture_flags(const mp2vg_parsed_t* p, uint32_t* flags, int32_t n);
 /* sequence headers of the parsed stream (see mp2vg_stream_headers_t) */
 int  mp2vg_parsed_stream_headers(const mp2vg_parsed_t* p, mp2vg_stream_headers_t* out);
 /* Independent shards for GOP sharding: shard[i] of each picture (decode order), numbered from 0.
@@ -474,6 +521,7 @@ int  mp2vg_scan_counts(const mp2vg_scan_t* s, int32_t* npics, uint64_t* nslices)
 const mp2vg_picture_t* mp2vg_scan_pictures(const mp2vg_scan_t* s);
 int  mp2vg_scan_display_order(const mp2vg_scan_t* s, int32_t* order, int32_t n);
 int  mp2vg_scan_gop_index(const mp2vg_scan_t* s, int32_t* gop, int32_t n);
+int  mp2vg_scan_picture_flags(const mp2vg_scan_t* s, uint32_t* flags, int32_t n); /* as mp2vg_parsed_picture_flags */
 int  mp2vg_scan_shards(const mp2vg_scan_t* s, int32_t* shard, int32_t n);
 int  mp2vg_scan_stream_headers(const mp2vg_scan_t* s, mp2vg_stream_headers_t* out);
 void mp2vg_scan_free(mp2vg_scan_t* s);
@@ -538,7 +586,9 @@ typedef struct mp2vg_gen_params {
     int32_t mix;                 /* 0: SURVEY §8d C2 mix; 1: intra only; 2: MC-heavy         */
     int32_t leading_b;           /* closed GOP starts I + (M-1) backward-only B pictures    */
     int32_t big_matrix_permille; /* probability of a quantiser-matrix entry > 128           */
-    int32_t reserved[5];
+    int32_t top_field_first;     /* 0, 1, or -1 = random per picture; written as 1 only in
+                                    pictures with progressive_frame = 0 (frame_pred_frame_dct = 0) */
+    int32_t reserved[4];
 } mp2vg_gen_params_t;
 
 void mp2vg_gen_default_params(mp2vg_gen_params_t* p);

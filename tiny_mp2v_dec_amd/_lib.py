@@ -57,8 +57,8 @@ class GenParams(ctypes.Structure):
         (n, ctypes.c_int32) for n in (
             "frame_pred_frame_dct", "alternate_scan", "q_scale_type", "intra_dc_precision", "coefs_min",
             "coefs_max", "intra_coefs_min", "intra_coefs_max", "big_level_permille", "escape_permille",
-            "quant_permille", "f_code", "mix", "leading_b", "big_matrix_permille")] + [
-        ("reserved", ctypes.c_int32 * 5)]
+            "quant_permille", "f_code", "mix", "leading_b", "big_matrix_permille", "top_field_first")] + [
+        ("reserved", ctypes.c_int32 * 4)]
 
 
 class Frame(ctypes.Structure):
@@ -121,6 +121,9 @@ class Tensor(ctypes.Structure):  # mp2vg_tensor_t
 
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 TENSOR_MAX_TAPS = 65
+FIELD_PROGRESSIVE, FIELD_TOP, FIELD_BOTTOM, FIELD_WEAVE = 0, 1, 2, 3  # MP2VG_FIELD_*
+FIELDS = {"progressive": FIELD_PROGRESSIVE, "top": FIELD_TOP, "bottom": FIELD_BOTTOM, "weave": FIELD_WEAVE}
+PIC_PROGRESSIVE_FRAME, PIC_TOP_FIELD_FIRST, PIC_REPEAT_FIRST_FIELD = 1, 2, 4  # MP2VG_PIC_*
 TENSOR_DTYPES = {"uint8": (TENSOR_U8, 1), "float16": (TENSOR_F16, 2), "bfloat16": (TENSOR_BF16, 2),
                  "float32": (TENSOR_F32, 4)}  # name -> (MP2VG_TENSOR_*, element size)
 
@@ -141,6 +144,7 @@ EXPORTS = [
     "mp2vg_export_coefficients", "mp2vg_export_matrix", "mp2vg_export_bytes", "mp2vg_export_slots",
     "mp2vg_export_planes",
     "mp2vg_tensor_weights", "mp2vg_tensor_bytes", "mp2vg_tensor_slots", "mp2vg_tensor_planes",
+    "mp2vg_tensor_slots_fields", "mp2vg_tensor_planes_field", "mp2vg_parsed_picture_flags", "mp2vg_scan_picture_flags",
     "mp2vg_scan_es", "mp2vg_scan_counts", "mp2vg_scan_pictures", "mp2vg_scan_display_order",
     "mp2vg_scan_gop_index", "mp2vg_scan_shards", "mp2vg_scan_stream_headers", "mp2vg_scan_free",
     "mp2vg_scan_parse_host", "mp2vg_batch_upload_es", "mp2vg_batch_record_counts",
@@ -217,6 +221,10 @@ def lib():
         "mp2vg_tensor_bytes": ([P(Config), P(Tensor), I32, P(U64)], ctypes.c_int),
         "mp2vg_tensor_slots": ([VP, P(I32), I32, P(Tensor), VP, U64], ctypes.c_int),
         "mp2vg_tensor_planes": ([I32, P(VP), P(I32), I32, I32, I32, P(Tensor), VP, U64], ctypes.c_int),
+        "mp2vg_tensor_slots_fields": ([VP, P(I32), P(I32), I32, P(Tensor), VP, U64], ctypes.c_int),
+        "mp2vg_tensor_planes_field": ([I32, P(VP), P(I32), I32, I32, I32, I32, P(Tensor), VP, U64], ctypes.c_int),
+        "mp2vg_parsed_picture_flags": ([VP, P(ctypes.c_uint32), I32], ctypes.c_int),
+        "mp2vg_scan_picture_flags": ([VP, P(ctypes.c_uint32), I32], ctypes.c_int),
         "mp2vg_scan_es": ([VP, U64, P(Config), P(VP)], ctypes.c_int),
         "mp2vg_scan_counts": ([VP, P(I32), P(U64)], ctypes.c_int),
         "mp2vg_scan_pictures": ([VP], VP),
@@ -320,6 +328,30 @@ def make_tensor(size, crop=None, dtype="float16", mean=None, std=None, layout="n
     x, y, w, h = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
     return Tensor(e.layout, e.matrix, e.chroma, x, y, w, h, int(size[0]), int(size[1]), TENSOR_DTYPES[name][0],
                   (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias), (ctypes.c_int32 * 4)())
+
+
+def field_mode(field):
+    """MP2VG_FIELD_* from "progressive" / "top" / "bottom" / "weave" or the integer itself."""
+    if isinstance(field, str):
+        if field not in FIELDS:
+            raise ValueError(f"field {field!r}: expected 'progressive', 'top', 'bottom' or 'weave'")
+        return FIELDS[field]
+    if int(field) not in FIELDS.values():
+        raise ValueError(f"field {field!r}: expected 0..3 (MP2VG_FIELD_*)")
+    return int(field)
+
+
+def field_modes(fields, n):
+    """The int32 field list of n frames from None (no list: all progressive), one mode for every
+    frame, or a sequence of n modes (names or integers)."""
+    if fields is None:
+        return None
+    if isinstance(fields, (str, int, np.integer)):
+        return np.full(n, field_mode(fields), np.int32)
+    out = np.array([field_mode(f) for f in fields], np.int32)
+    if len(out) != n:
+        raise ValueError("fields must hold one mode per slot")
+    return out
 
 
 def tensor_shape(t, n):

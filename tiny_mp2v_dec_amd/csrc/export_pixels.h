@@ -76,4 +76,31 @@ __device__ __forceinline__ void chroma4(const uint8_t* __restrict__ rj, const ui
     c[3] = ((odd ? 2 * s2 : a12) + 4) >> 3;
 }
 
+// chroma4 with the vertical taps as arguments, wv0 + wv1 = 8 (the tensor export's field modes,
+// include/mp2vg.h): (wv0 (C[j][k] + C[j][k1]) + wv1 (C[j1][k] + C[j1][k1]) + 8) >> 4, one rounding.
+// wv0, wv1 = 6, 2 is chroma4's 4:2:0 result and 8, 0 its 4:2:2 result, bit for bit.  NEAREST and
+// 4:4:4 have no taps: chroma4.
+template <int CF, bool LINEAR>
+__device__ __forceinline__ void chroma4w(const uint8_t* __restrict__ rj, const uint8_t* __restrict__ rj1, int x0,
+                                         int stride, int cw, int wv0, int wv1, int c[4]) {
+    if (CF == 3 || !LINEAR) {
+        chroma4<CF, LINEAR>(rj, rj1, x0, stride, cw, c);
+        return;
+    }
+    const int c0 = x0 >> 1;
+    const bool odd = x0 & 1;
+    const uint32_t va = load4(rj, c0, stride);
+    const uint32_t vb = CF == 1 ? load4(rj1, c0, stride) : 0u;
+    const int s0 = CF == 1 ? __mul24(wv0, byte_of(va, 0)) + __mul24(wv1, byte_of(vb, 0)) : 8 * byte_of(va, 0);
+    int s1 = CF == 1 ? __mul24(wv0, byte_of(va, 1)) + __mul24(wv1, byte_of(vb, 1)) : 8 * byte_of(va, 1);
+    int s2 = CF == 1 ? __mul24(wv0, byte_of(va, 2)) + __mul24(wv1, byte_of(vb, 2)) : 8 * byte_of(va, 2);
+    if (c0 + 1 > cw - 1) s1 = s0;  // k1 clamps to the coded chroma plane
+    if (c0 + 2 > cw - 1) s2 = s1;
+    const int a01 = s0 + s1, a12 = s1 + s2;
+    c[0] = ((odd ? a01 : 2 * s0) + 8) >> 4;
+    c[1] = ((odd ? 2 * s1 : a01) + 8) >> 4;
+    c[2] = ((odd ? a12 : 2 * s1) + 8) >> 4;
+    c[3] = ((odd ? 2 * s2 : a12) + 8) >> 4;
+}
+
 }  // namespace mp2vg

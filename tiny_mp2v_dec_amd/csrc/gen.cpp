@@ -52,7 +52,7 @@ const char* find_code(const vlc_code* tab, int n, int a) {
 struct PicParams {
     int pct;
     int tref;
-    int alt, qst, prec, fpfd;
+    int alt, qst, prec, fpfd, tff;
     int fcode[2][2];
     bool leading_b;  // backward-only B (closed GOP)
     uint8_t qme[4][64];
@@ -412,7 +412,7 @@ void Writer::picture(const PicParams& pp) {
         for (int t = 0; t < 2; t++) bw.put(pp.fcode[s][t], 4);
     bw.put(pp.prec, 2);
     bw.put(3, 2);  // frame picture
-    bw.put(0, 1);  // top_field_first
+    bw.put(pp.tff, 1);  // top_field_first
     bw.put(pp.fpfd, 1);
     bw.put(0, 1);  // concealment_motion_vectors
     bw.put(pp.qst, 1);
@@ -451,6 +451,9 @@ int Writer::run(std::vector<uint8_t>& out) {
             pp.qst = P.q_scale_type >= 0 ? P.q_scale_type : (int)(rng.next() & 1);
             pp.prec = P.intra_dc_precision >= 0 ? P.intra_dc_precision : rng.uni(0, 3);
             pp.fpfd = P.frame_pred_frame_dct;
+            // (progressive_frame = fpfd; the RNG is drawn only for -1, so other streams keep their bytes)
+            pp.tff = P.top_field_first < 0 ? (int)(rng.next() & 1) : P.top_field_first ? 1 : 0;
+            if (pp.fpfd) pp.tff = 0;
             for (int s = 0; s < 2; s++)
                 for (int t = 0; t < 2; t++) pp.fcode[s][t] = 15;
             if (pp.pct >= 2) pp.fcode[0][0] = pp.fcode[0][1] = P.f_code;

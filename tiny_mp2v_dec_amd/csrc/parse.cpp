@@ -42,6 +42,7 @@ struct PictureHdr {
     int q_scale_type = 0;
     int intra_vlc_format = 0;
     int alternate_scan = 0;
+    int top_field_first = 0, repeat_first_field = 0, progressive_frame = 0;
     bool have_pcext = false;
     bool have_qme = false;
     int qme_load[4] = {0, 0, 0, 0};
@@ -465,6 +466,7 @@ struct ParsedImpl {
     std::vector<uint32_t, NoInitAlloc<uint32_t>> coefs;
     std::vector<int32_t> display;
     std::vector<int32_t> gop;
+    std::vector<uint32_t> flags;  // MP2VG_PIC_* of each picture (mp2vg_parsed_picture_flags)
     std::vector<int32_t> shard;  // independent decode-order runs (mp2vg_parsed_shards)
     int32_t nshards = 0;
     mp2vg_stream_headers_t hdrs{};
@@ -693,12 +695,15 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
                     for (int t = 0; t < 2; t++) h.f_code[s][t] = (int)br.read(4);
                 h.intra_dc_precision = (int)br.read(2);
                 h.picture_structure = (int)br.read(2);
-                br.skip(1);  // top_field_first
+                h.top_field_first = (int)br.read(1);
                 h.frame_pred_frame_dct = (int)br.read(1);
                 h.concealment_motion_vectors = (int)br.read(1);
                 h.q_scale_type = (int)br.read(1);
                 h.intra_vlc_format = (int)br.read(1);
                 h.alternate_scan = (int)br.read(1);
+                h.repeat_first_field = (int)br.read(1);
+                br.skip(1);  // chroma_420_type
+                h.progressive_frame = (int)br.read(1);
                 h.have_pcext = true;
             } else if (id == 3 && cur >= 0) {  // quant_matrix_extension (:133-152)
                 PictureHdr& h = C.pics[cur].hdr;
@@ -803,6 +808,9 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         d.temporal_reference = P.hdr.temporal_reference;
         memcpy(d.W, P.W, sizeof d.W);
         res->gop.push_back(P.gop);
+        res->flags.push_back((P.hdr.progressive_frame ? MP2VG_PIC_PROGRESSIVE_FRAME : 0u) |
+                             (P.hdr.top_field_first ? MP2VG_PIC_TOP_FIELD_FIRST : 0u) |
+                             (P.hdr.repeat_first_field ? MP2VG_PIC_REPEAT_FIRST_FIELD : 0u));
     }
     res->hdrs = C.hdrs;
     // ---- independent shards: a new one starts at p when no picture from p on predicts from a
@@ -1004,6 +1012,11 @@ extern "C" int mp2vg_parsed_gop_index(const mp2vg_parsed_t* p, int32_t* gop, int
     if (!p->gop.empty()) memcpy(gop, p->gop.data(), p->gop.size() * 4);
     return (int)p->gop.size();
 }
+extern "C" int mp2vg_parsed_picture_flags(const mp2vg_parsed_t* p, uint32_t* flags, int32_t n) {
+    if (!p || !flags || n < (int32_t)p->flags.size()) return MP2VG_E_INVALID;
+    if (!p->flags.empty()) memcpy(flags, p->flags.data(), p->flags.size() * 4);
+    return (int)p->flags.size();
+}
 extern "C" int mp2vg_parsed_stream_headers(const mp2vg_parsed_t* p, mp2vg_stream_headers_t* out) {
     if (!p || !out) return MP2VG_E_INVALID;
     *out = p->hdrs;
@@ -1113,6 +1126,7 @@ extern "C" int mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_confi
     S->pics = std::move(res.pics);
     S->display = std::move(res.display);
     S->gop = std::move(res.gop);
+    S->flags = std::move(res.flags);
     S->shard = std::move(res.shard);
     S->nshards = res.nshards;
     S->hdrs = res.hdrs;
@@ -1179,6 +1193,11 @@ extern "C" int mp2vg_scan_gop_index(const mp2vg_scan_t* s, int32_t* gop, int32_t
     if (!s || !gop || n < (int32_t)s->gop.size()) return MP2VG_E_INVALID;
     if (!s->gop.empty()) memcpy(gop, s->gop.data(), s->gop.size() * 4);
     return (int)s->gop.size();
+}
+extern "C" int mp2vg_scan_picture_flags(const mp2vg_scan_t* s, uint32_t* flags, int32_t n) {
+    if (!s || !flags || n < (int32_t)s->flags.size()) return MP2VG_E_INVALID;
+    if (!s->flags.empty()) memcpy(flags, s->flags.data(), s->flags.size() * 4);
+    return (int)s->flags.size();
 }
 extern "C" int mp2vg_scan_shards(const mp2vg_scan_t* s, int32_t* shard, int32_t n) {
     if (!s || !shard || n < (int32_t)s->shard.size()) return MP2VG_E_INVALID;

@@ -13,6 +13,7 @@ struct mp2vg_scan {
     mp2vg::SpGeom g{};
     std::vector<mp2vg_picture_t> pics;
     std::vector<int32_t> display, gop, shard;
+    std::vector<uint32_t> flags;           // MP2VG_PIC_* per picture
     int32_t nshards = 0;
     mp2vg_stream_headers_t hdrs{};
     std::vector<mp2vg::SpPicHdr> hdr;      // per picture

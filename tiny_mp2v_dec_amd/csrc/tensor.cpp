@@ -1,5 +1,6 @@
 // tensor.cpp — host entry points of the tensor export that enqueue the kernel (tensor.hip):
-// mp2vg_tensor_slots and mp2vg_tensor_planes.  The host-only part (tap tables, validation, sizes)
+// mp2vg_tensor_slots_fields and mp2vg_tensor_planes_field, and mp2vg_tensor_slots and
+// mp2vg_tensor_planes, their all-PROGRESSIVE cases.  The host-only part (tap tables, validation, sizes)
 // lives in runtime.cpp; the context's side (slot table, staging ring, events) is the RGB export's.
 #include <hip/hip_runtime.h>
 
@@ -46,8 +47,21 @@ static int check_dst(const mp2vg_tensor_t* t, int32_t n, int32_t elem, const voi
     return MP2VG_OK;
 }
 
-extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t n, const mp2vg_tensor_t* t, void* dst,
-                                  uint64_t dst_bytes) {
+// a field mode's preconditions on the coded frame (include/mp2vg.h "Field modes")
+static int check_field(int32_t field, int32_t cf, int32_t coded_h) {
+    if (field < MP2VG_FIELD_PROGRESSIVE || field > MP2VG_FIELD_WEAVE) {
+        set_error("tensor: field mode outside MP2VG_FIELD_*");
+        return MP2VG_E_INVALID;
+    }
+    if (field != MP2VG_FIELD_PROGRESSIVE && (coded_h & (cf == 1 ? 3 : 1))) {
+        set_error("tensor: a field mode needs an even coded height (4:2:0: a multiple of 4)");
+        return MP2VG_E_INVALID;
+    }
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_tensor_slots_fields(mp2vg_ctx_t* c, const int32_t* slots, const int32_t* fields, int32_t n,
+                                         const mp2vg_tensor_t* t, void* dst, uint64_t dst_bytes) {
     if (!c || !slots || !t || !dst || n <= 0 || n > kTensorMaxFrames) return MP2VG_E_INVALID;
     ExportSource s;
     export_source(c, &s);
@@ -56,18 +70,28 @@ extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t 
             set_error("tensor: slot out of range");
             return MP2VG_E_INVALID;
         }
+    // a list of PROGRESSIVE only is the launch without field modes (mp2vg_tensor_slots)
+    bool field_modes = false;
+    for (int i = 0; fields && i < n; i++) {
+        if (int rc = check_field(fields[i], s.cf, s.ph)) return rc;
+        field_modes |= fields[i] != MP2VG_FIELD_PROGRESSIVE;
+    }
     int32_t rect[4], elem;
     if (int rc = check_tensor(t, s.pw, s.ph, rect, &elem)) return rc;
     if (int rc = check_dst(t, n, elem, dst, dst_bytes)) return rc;
+    // staged in front of the tables: the slot list, then the field list
     TensorTables tt;
-    if (int rc = tensor_tables(rect, t->out_w, t->out_h, (size_t)n, &tt)) return rc;
+    if (int rc = tensor_tables(rect, t->out_w, t->out_h, (size_t)n * (field_modes ? 2 : 1), &tt)) return rc;
     memcpy(tt.blob.data(), slots, sizeof(int32_t) * n);
+    if (field_modes) memcpy(tt.blob.data() + n, fields, sizeof(int32_t) * n);
     HIPCHK(hipSetDevice(s.device));
     TensorArgs a;
     memset(&a, 0, sizeof a);
     const int32_t* d = nullptr;
     if (int rc = export_stage_slots(c, tt.blob.data(), (int32_t)tt.blob.size(), &d)) return rc;
     a.slots = d;
+    a.fields = field_modes ? d + n : nullptr;
+    a.coded_h = s.ph;
     a.ftab = s.ftab;
     for (int p = 0; p < 3; p++) {
         a.plane_off[p] = s.plane_off[p];
@@ -77,17 +101,23 @@ extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t 
     a.ch = s.ch;
     tensor_args(&a, t, rect, tt, d, dst);
     // the list's copy is in flight: its events are recorded whether or not the launch succeeded
-    const hipError_t le = launch_tensor(s.cf, t->layout, t->chroma, t->dtype, a, tt.nsegs, n, s.stream);
+    const hipError_t le = launch_tensor(s.cf, t->layout, t->chroma, t->dtype, field_modes, a, tt.nsegs, n, s.stream);
     const int rc = export_enqueued(c);
     HIPCHK(le);
     return rc;
 }
 
-extern "C" int mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3], int32_t cf,
-                                   int32_t coded_w, int32_t coded_h, const mp2vg_tensor_t* t, void* dst,
-                                   uint64_t dst_bytes) {
+extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t n, const mp2vg_tensor_t* t, void* dst,
+                                  uint64_t dst_bytes) {
+    return mp2vg_tensor_slots_fields(c, slots, nullptr, n, t, dst, dst_bytes);
+}
+
+extern "C" int mp2vg_tensor_planes_field(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                                         int32_t cf, int32_t coded_w, int32_t coded_h, int32_t field,
+                                         const mp2vg_tensor_t* t, void* dst, uint64_t dst_bytes) {
     if (!planes || !stride || !t || !dst || device < 0 || cf < 1 || cf > 3 || coded_w <= 0 || coded_h <= 0)
         return MP2VG_E_INVALID;
+    if (int rc = check_field(field, cf, coded_h)) return rc;
     if ((cf < 3 && (coded_w & 1)) || (cf == 1 && (coded_h & 1))) {
         set_error("tensor: odd coded size with subsampled chroma");
         return MP2VG_E_INVALID;
@@ -118,11 +148,21 @@ extern "C" int mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3
         }
         a.cw = cw;
         a.ch = ch;
+        a.field = field;
+        a.coded_h = coded_h;
         tensor_args(&a, t, rect, tt, d, dst);
-        e = launch_tensor(cf, t->layout, t->chroma, t->dtype, a, tt.nsegs, 1, nullptr);
+        e = launch_tensor(cf, t->layout, t->chroma, t->dtype, field != MP2VG_FIELD_PROGRESSIVE, a, tt.nsegs, 1,
+                          nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     hipFree(d);
     HIPCHK(e);
     return MP2VG_OK;
+}
+
+extern "C" int mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3], int32_t cf,
+                                   int32_t coded_w, int32_t coded_h, const mp2vg_tensor_t* t, void* dst,
+                                   uint64_t dst_bytes) {
+    return mp2vg_tensor_planes_field(device, planes, stride, cf, coded_w, coded_h, MP2VG_FIELD_PROGRESSIVE, t, dst,
+                                     dst_bytes);
 }

@@ -25,9 +25,16 @@
 // (from L2 mostly), against write + read of 3 B/pixel RGB and a 12 B/pixel float intermediate on
 // the unfused path.
 //
-// Static resources (hipcc -O3, --offload-arch=gfx950, all 40 variants): 60-68 VGPRs, no scratch,
-// 24576 B LDS per workgroup, which sets 6 waves per SIMD (measured speed, also of the one-row
-// split this replaced: profiles/export/tensor.md).
+// Field modes (mp2vg_tensor_slots_fields, include/mp2vg.h "Field modes"): the kernel is
+// instantiated twice.  FIELDS = false is the walk above for launches whose frames are all
+// PROGRESSIVE; FIELDS = true reads the mode of its frame and changes the vertical pass only: field
+// chroma siting per line, and for TOP / BOTTOM a walk over the field's lines alone, with the rows
+// between them made from the rounded average of two converted lines (comment at the walk).
+//
+// Static resources (hipcc -O3, --offload-arch=gfx950, 40 variants each): 60-68 VGPRs without
+// field modes, 65-72 with, no scratch, 24576 B LDS per workgroup, which sets 6 waves per SIMD
+// (up to 80 VGPRs keep that; measured speed, also of the one-row split this replaced:
+// profiles/export/tensor.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -37,13 +44,9 @@
 
 namespace mp2vg {
 
-// R, G, B (0..255) of pixels x0 .. x0 + 3: the RGB export's pixels4, unpacked
-template <int CF, bool LINEAR>
-__device__ __forceinline__ void rgb4(const TensorArgs& a, const Rows& r, int x0, int R[4], int G[4], int B[4]) {
-    const uint32_t yv = load4(r.y, x0, a.stride[0]);
-    int cb[4], cr[4];
-    chroma4<CF, LINEAR>(r.cb, r.cb1, x0, a.stride[1], a.cw, cb);
-    chroma4<CF, LINEAR>(r.cr, r.cr1, x0, a.stride[2], a.cw, cr);
+// the RGB export's matrix arithmetic on 4 pixels: luma dword yv, 8-bit chroma cb / cr -> R, G, B (0..255)
+__device__ __forceinline__ void matrix4(const TensorArgs& a, uint32_t yv, const int cb[4], const int cr[4], int R[4],
+                                        int G[4], int B[4]) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int yy = __mul24(a.cy, byte_of(yv, i));
@@ -54,6 +57,48 @@ __device__ __forceinline__ void rgb4(const TensorArgs& a, const Rows& r, int x0,
         G[i] = (int)clamp8((yy + tg) >> 14);
         B[i] = (int)clamp8((yy + tb) >> 14);
     }
+}
+
+// R, G, B (0..255) of pixels x0 .. x0 + 3: the RGB export's pixels4, unpacked
+template <int CF, bool LINEAR>
+__device__ __forceinline__ void rgb4(const TensorArgs& a, const Rows& r, int x0, int R[4], int G[4], int B[4]) {
+    const uint32_t yv = load4(r.y, x0, a.stride[0]);
+    int cb[4], cr[4];
+    chroma4<CF, LINEAR>(r.cb, r.cb1, x0, a.stride[1], a.cw, cb);
+    chroma4<CF, LINEAR>(r.cr, r.cr1, x0, a.stride[2], a.cw, cr);
+    matrix4(a, yv, cb, cr, R, G, B);
+}
+
+// Line y of the frame for the field modes (include/mp2vg.h "Field modes"): L_{y & 1}[y] with the
+// field chroma when `field_chroma`, else the progressive line.  Everything that depends on y is
+// uniform over the workgroup: the chroma rows j, j1 and the vertical taps wv0, wv1 (eighths).
+template <int CF, bool LINEAR>
+__device__ __forceinline__ void line4(const TensorArgs& a, const uint8_t* const pl[3], int y, bool field_chroma, int x0,
+                                      int R[4], int G[4], int B[4]) {
+    int j = y, j1 = y, wv1 = 0;
+    if (CF == 1) {
+        if (field_chroma) {
+            j = 2 * (y >> 2) + (y & 1);  // the chroma row of the same field
+            j1 = (y & 2) ? j + 2 : j - 2;
+            if (j1 < 0 || j1 > a.ch - 1) j1 = j;
+            wv1 = (y & 3) == 1 || (y & 3) == 2 ? 3 : 1;
+        } else {
+            j = y >> 1;
+            j1 = min(max(j + ((y & 1) ? 1 : -1), 0), a.ch - 1);
+            wv1 = 2;  // (6 A + 2 B + 8) >> 4 = (3 A + B + 4) >> 3
+        }
+    }
+    const uint32_t yv = load4(pl[0] + (size_t)y * a.stride[0], x0, a.stride[0]);
+    int cb[4], cr[4];
+    chroma4w<CF, LINEAR>(pl[1] + (size_t)j * a.stride[1], pl[1] + (size_t)j1 * a.stride[1], x0, a.stride[1], a.cw,
+                         8 - wv1, wv1, cb);
+    chroma4w<CF, LINEAR>(pl[2] + (size_t)j * a.stride[2], pl[2] + (size_t)j1 * a.stride[2], x0, a.stride[2], a.cw,
+                         8 - wv1, wv1, cr);
+    matrix4(a, yv, cb, cr, R, G, B);
+}
+
+__device__ __forceinline__ uint32_t pack4(const int v[4]) {
+    return (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)v[3] << 24;
 }
 
 struct alignas(8) V4 {
@@ -67,7 +112,9 @@ __device__ __forceinline__ uint16_t bf16_rne(float f) {
     return (uint16_t)(u >> 16);
 }
 
-template <int CF, bool LINEAR, bool PACKED, int DTYPE>
+// FIELDS = false: every frame PROGRESSIVE (mp2vg_tensor_slots / mp2vg_tensor_planes); true: the
+// frame's MP2VG_FIELD_* mode picks the row walk of the vertical pass
+template <int CF, bool LINEAR, bool PACKED, int DTYPE, bool FIELDS>
 __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     __shared__ alignas(8) int16_t lds[2][3][kTensorSegCols];
     const int tid = (int)threadIdx.x;
@@ -87,29 +134,88 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     const int nrows = max(f0 + c0, f1 + c1) - f0;
     const int32_t* qv0 = a.vw + (size_t)oy * a.vmax;
     const int32_t* qv1 = qv0 + (two ? a.vmax : 0);
+    // field modes (uniform over the workgroup).  WEAVE and PROGRESSIVE walk every row of the union
+    // as above, with the line's own chroma siting.  TOP / BOTTOM (parity par) walk only the field's
+    // lines z = z0, z0 + 2 .. z1: from the line above the first tap row when that row is an
+    // interpolated one (unless it is row 0 of the frame: a = b, the average of the line with itself)
+    // to the line below the last tap row (past the frame's last field line zmax it is that line
+    // again: b = a).  Line z weighs in as row z, and its rounded average with the previous line,
+    // formed as 8-bit values, as row z - 1; a row outside the union has weight 0.
+    // (readfirstlane: the choice between the list and the argument is a vector load to the compiler;
+    // as a scalar the mode keeps the walk's bounds, rows and weights in SGPRs)
+    const int mode = !FIELDS ? MP2VG_FIELD_PROGRESSIVE
+                             : __builtin_amdgcn_readfirstlane(a.fields ? a.fields[f] : a.field);
+    const bool single = mode == MP2VG_FIELD_TOP || mode == MP2VG_FIELD_BOTTOM;
+    const int par = mode == MP2VG_FIELD_BOTTOM ? 1 : 0;
+    const int Y0 = a.src_y + f0, Yl = Y0 + nrows - 1;
+    const int z0 = single ? max(Y0 - ((Y0 & 1) != par ? 1 : 0), par) : Y0;
+    const int z1 = single ? Yl + ((Yl & 1) != par ? 1 : 0) : Yl;
+    const int zmax = single ? a.coded_h - 2 + par : Yl;
+    const int step = single ? 2 : 1;
+    // weight of row k of the union for the two output rows: the loads are unconditional (the index
+    // clamped into the row's vmax entries), so the scalar loads of one line issue together
+    auto wt0 = [&](int k) {
+        const int q = qv0[min(max(k, 0), a.vmax - 1)];
+        return k >= 0 && k < c0 ? q : 0;
+    };
+    auto wt1 = [&](int k) {
+        const int q = qv1[min(max(k + f0 - f1, 0), a.vmax - 1)];
+        return k + f0 - f1 >= 0 && k + f0 - f1 < c1 ? q : 0;
+    };
     for (int u = tid; u < nunits; u += 256) {
         const int x0 = a.src_x + base + 4 * u;
         int aR[2][4] = {}, aG[2][4] = {}, aB[2][4] = {};
-        for (int k = 0; k < nrows; k++) {
-            const int y = a.src_y + f0 + k;
-            Rows r;
-            const int j = CF == 1 ? y >> 1 : y;
-            const int j1 = CF == 1 && LINEAR ? min(max(j + ((y & 1) ? 1 : -1), 0), a.ch - 1) : j;
-            r.y = pl[0] + (size_t)y * a.stride[0];
-            r.cb = pl[1] + (size_t)j * a.stride[1];
-            r.cr = pl[2] + (size_t)j * a.stride[2];
-            r.cb1 = pl[1] + (size_t)j1 * a.stride[1];
-            r.cr1 = pl[2] + (size_t)j1 * a.stride[2];
-            int R[4], G[4], B[4];
-            rgb4<CF, LINEAR>(a, r, x0, R, G, B);
-            const int k1 = f0 + k - f1;
-            const int q0 = k < c0 ? qv0[k] : 0;
-            const int q1 = k1 >= 0 && k1 < c1 ? qv1[k1] : 0;
+        if (!FIELDS) {
+            for (int k = 0; k < nrows; k++) {
+                const int y = a.src_y + f0 + k;
+                Rows r;
+                const int j = CF == 1 ? y >> 1 : y;
+                const int j1 = CF == 1 && LINEAR ? min(max(j + ((y & 1) ? 1 : -1), 0), a.ch - 1) : j;
+                r.y = pl[0] + (size_t)y * a.stride[0];
+                r.cb = pl[1] + (size_t)j * a.stride[1];
+                r.cr = pl[2] + (size_t)j * a.stride[2];
+                r.cb1 = pl[1] + (size_t)j1 * a.stride[1];
+                r.cr1 = pl[2] + (size_t)j1 * a.stride[2];
+                int R[4], G[4], B[4];
+                rgb4<CF, LINEAR>(a, r, x0, R, G, B);
+                const int k1 = f0 + k - f1;
+                const int q0 = k < c0 ? qv0[k] : 0;
+                const int q1 = k1 >= 0 && k1 < c1 ? qv1[k1] : 0;
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                aR[0][i] += __mul24(q0, R[i]), aR[1][i] += __mul24(q1, R[i]);
-                aG[0][i] += __mul24(q0, G[i]), aG[1][i] += __mul24(q1, G[i]);
-                aB[0][i] += __mul24(q0, B[i]), aB[1][i] += __mul24(q1, B[i]);
+                for (int i = 0; i < 4; i++) {
+                    aR[0][i] += __mul24(q0, R[i]), aR[1][i] += __mul24(q1, R[i]);
+                    aG[0][i] += __mul24(q0, G[i]), aG[1][i] += __mul24(q1, G[i]);
+                    aB[0][i] += __mul24(q0, B[i]), aB[1][i] += __mul24(q1, B[i]);
+                }
+            }
+        } else {
+            uint32_t prev[3] = {0u, 0u, 0u};  // the previous field line, a dword of 4 pixels per channel
+            for (int z = z0; z <= z1; z += step) {
+                int R[4], G[4], B[4];
+                line4<CF, LINEAR>(a, pl, min(z, zmax), mode != MP2VG_FIELD_PROGRESSIVE, x0, R, G, B);
+                const int q0 = wt0(z - Y0), q1 = wt1(z - Y0);
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    aR[0][i] += __mul24(q0, R[i]), aR[1][i] += __mul24(q1, R[i]);
+                    aG[0][i] += __mul24(q0, G[i]), aG[1][i] += __mul24(q1, G[i]);
+                    aB[0][i] += __mul24(q0, B[i]), aB[1][i] += __mul24(q1, B[i]);
+                }
+                if (single) {
+                    const uint32_t cur[3] = {pack4(R), pack4(G), pack4(B)};
+                    if (z == z0) prev[0] = cur[0], prev[1] = cur[1], prev[2] = cur[2];
+                    // v_lerp_u8: per byte (a + b + 1) >> 1
+                    const uint32_t mr = __builtin_amdgcn_lerp(prev[0], cur[0], 0x01010101u);
+                    const uint32_t mg = __builtin_amdgcn_lerp(prev[1], cur[1], 0x01010101u);
+                    const uint32_t mb = __builtin_amdgcn_lerp(prev[2], cur[2], 0x01010101u);
+                    const int m0 = wt0(z - Y0 - 1), m1 = wt1(z - Y0 - 1);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        aR[0][i] += __mul24(m0, byte_of(mr, i)), aR[1][i] += __mul24(m1, byte_of(mr, i));
+                        aG[0][i] += __mul24(m0, byte_of(mg, i)), aG[1][i] += __mul24(m1, byte_of(mg, i));
+                        aB[0][i] += __mul24(m0, byte_of(mb, i)), aB[1][i] += __mul24(m1, byte_of(mb, i));
+                    }
+                    prev[0] = cur[0], prev[1] = cur[1], prev[2] = cur[2];
+                }
             }
         }
 #pragma unroll
@@ -171,44 +277,47 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     }
 }
 
-template <int CF, bool LINEAR, bool PACKED>
+template <int CF, bool LINEAR, bool PACKED, bool FIELDS>
 static void launch_dtype(int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
     const dim3 block(256, 1, 1);
     if (dtype == MP2VG_TENSOR_U8)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8, FIELDS>), grid, block, 0, stream, a);
     else if (dtype == MP2VG_TENSOR_F16)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16, FIELDS>), grid, block, 0, stream, a);
     else if (dtype == MP2VG_TENSOR_BF16)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16, FIELDS>), grid, block, 0, stream, a);
     else
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32, FIELDS>), grid, block, 0, stream, a);
 }
 
-template <int CF>
+template <int CF, bool FIELDS>
 static void launch_cf(int layout, int chroma, int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
     const bool lin = chroma == MP2VG_EXPORT_CHROMA_LINEAR && CF != 3;  // 4:4:4: LINEAR is NEAREST
     if (layout == MP2VG_EXPORT_RGB_PACKED) {
         if (lin)
-            launch_dtype<CF, CF != 3, true>(dtype, a, grid, stream);
+            launch_dtype<CF, CF != 3, true, FIELDS>(dtype, a, grid, stream);
         else
-            launch_dtype<CF, false, true>(dtype, a, grid, stream);
+            launch_dtype<CF, false, true, FIELDS>(dtype, a, grid, stream);
     } else {
         if (lin)
-            launch_dtype<CF, CF != 3, false>(dtype, a, grid, stream);
+            launch_dtype<CF, CF != 3, false, FIELDS>(dtype, a, grid, stream);
         else
-            launch_dtype<CF, false, false>(dtype, a, grid, stream);
+            launch_dtype<CF, false, false, FIELDS>(dtype, a, grid, stream);
     }
 }
 
-hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, const TensorArgs& a, int nsegs, int n,
-                         hipStream_t stream) {
+hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, const TensorArgs& a, int nsegs,
+                         int n, hipStream_t stream) {
     const dim3 grid((unsigned)nsegs, (unsigned)((a.out_h + 1) / 2), (unsigned)n);
     if (cf == 1)
-        launch_cf<1>(layout, chroma, dtype, a, grid, stream);
+        field_modes ? launch_cf<1, true>(layout, chroma, dtype, a, grid, stream)
+                    : launch_cf<1, false>(layout, chroma, dtype, a, grid, stream);
     else if (cf == 2)
-        launch_cf<2>(layout, chroma, dtype, a, grid, stream);
+        field_modes ? launch_cf<2, true>(layout, chroma, dtype, a, grid, stream)
+                    : launch_cf<2, false>(layout, chroma, dtype, a, grid, stream);
     else
-        launch_cf<3>(layout, chroma, dtype, a, grid, stream);
+        field_modes ? launch_cf<3, true>(layout, chroma, dtype, a, grid, stream)
+                    : launch_cf<3, false>(layout, chroma, dtype, a, grid, stream);
     return hipGetLastError();
 }
 

@@ -22,6 +22,8 @@ constexpr int kTensorSegCols = 2048;
 //                 [base, base + kTensorSegCols)
 //   hfirst / hw: horizontal taps of output column o: hw[o * hmax + k], zero from the column's tap
 //                 count on (the kernel runs all hmax); vfirst / vcount / vw: the rows'
+//   fields[n]: MP2VG_FIELD_* of each frame, or null: every frame in mode `field`.  Read by the
+//                 field-mode kernel only (launch_tensor's field_modes).
 struct TensorArgs {
     const uint64_t* ftab;
     const int32_t* slots;
@@ -36,17 +38,23 @@ struct TensorArgs {
     int32_t hmax, vmax;
     float scale[3], bias[3];
     void* dst;
+    // field modes, behind the arguments of the kernel without them (whose code they leave as it was)
+    const int32_t* fields;
+    int32_t field;
+    int32_t coded_h;
 };
 
-// cf 1..3; layout, chroma, dtype of the mp2vg_tensor_t; grid = (nsegs, row pairs, n)
-hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, const TensorArgs& a, int nsegs, int n,
-                         hipStream_t stream);
+// cf 1..3; layout, chroma, dtype of the mp2vg_tensor_t; grid = (nsegs, row pairs, n).
+// field_modes = false: every frame PROGRESSIVE, the kernel without the field row walk.
+hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, const TensorArgs& a, int nsegs,
+                         int n, hipStream_t stream);
 
 // host-only side (runtime.cpp)
 // checks t against a coded size; the source rectangle in rect[4] (x, y, w, h) and the element size
 int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int32_t rect[4], int32_t* elem);
 // The int32 tables of a validated tensor export, behind `lead` entries left for the caller (the
-// slot list): segs, hfirst, hw, vfirst, vcount, vw.  off[6] = the index of each in blob.
+// slot list, then the field list of a launch with field modes): segs, hfirst, hw, vfirst, vcount,
+// vw.  off[6] = the index of each in blob.
 struct TensorTables {
     std::vector<int32_t> blob;
     size_t off[6];

@@ -70,6 +70,9 @@ class Parsed:
             gop = (ctypes.c_int32 * max(n, 1))()
             lib().mp2vg_parsed_gop_index(h, gop, n)
             self.gop = np.array(gop[:n], dtype=np.int32)
+            flags = (ctypes.c_uint32 * max(n, 1))()
+            check_count(lib().mp2vg_parsed_picture_flags(h, flags, n), "parsed_picture_flags")
+            self.flags = np.array(flags[:n], dtype=np.uint32)  # MP2VG_PIC_* per picture, decode order
             shard = (ctypes.c_int32 * max(n, 1))()
             self.nshards = check_count(lib().mp2vg_parsed_shards(h, shard, n), "parsed_shards")
             self.shard = np.array(shard[:n], dtype=np.int32)
@@ -105,6 +108,9 @@ class Scan:
         gop = (ctypes.c_int32 * max(n, 1))()
         lib().mp2vg_scan_gop_index(self.h, gop, n)
         self.gop = np.array(gop[:n], dtype=np.int32)
+        flags = (ctypes.c_uint32 * max(n, 1))()
+        check_count(lib().mp2vg_scan_picture_flags(self.h, flags, n), "scan_picture_flags")
+        self.flags = np.array(flags[:n], dtype=np.uint32)  # MP2VG_PIC_* per picture, decode order
         shard = (ctypes.c_int32 * max(n, 1))()
         self.nshards = check_count(lib().mp2vg_scan_shards(self.h, shard, n), "scan_shards")
         self.shard = np.array(shard[:n], dtype=np.int32)
@@ -346,27 +352,33 @@ class DeviceContext:
         return t
 
     def export_tensor(self, slots, size, crop=None, dtype="float16", mean=None, std=None, layout="nchw",
-                      chroma="linear", matrix=1, out=None, sync=True):
+                      chroma="linear", matrix=1, out=None, sync=True, fields=None):
         """Frames of `slots` (any order, repeats allowed) as one model-input tensor on this
-        context's device (mp2vg_tensor_slots: one fused kernel launch): cropped to crop = (x, y, w,
+        context's device (mp2vg_tensor_slots_fields: one fused kernel launch): cropped to crop = (x, y, w,
         h) in luma pixels (None: the coded frame), resized to size = (width, height) with the
         bit-exact antialiased triangle filter of include/mp2vg.h, normalised per channel and cast to
         dtype (torch.float16 / "float16", bfloat16, float32 or uint8).  With mean / std (0..1
         units) the value is (x / 255 - mean) / std, computed as fmaf(x, scale, bias) with scale =
         float32(1 / (255 std)), bias = float32(-mean / std); without them x / 255 (uint8: x).
         (n, 3, h, w) for layout "nchw", (n, h, w, 3) for "nhwc"; chroma and matrix as export_rgb.
-        Writes into `out` when given.
+        Writes into `out` when given.  fields: the field mode of interlaced frames (include/mp2vg.h
+        "Field modes"): None, one of "progressive" / "top" / "bottom" / "weave" for every frame, or
+        one of those (or the MP2VG_FIELD_* integers) per slot; a slot listed twice with "top" and
+        "bottom" gives both fields of its picture.
 
         Stream ordering is export_rgb's: the export runs on the context's own stream behind the
         decodes enqueued so far; work torch has enqueued on `out` must have finished before the
         call, and with sync=False torch must not read the tensor before synchronize().  At most
         65535 slots per call."""
         slots = np.ascontiguousarray(slots, np.int32).ravel()
+        modes = _lib.field_modes(fields, len(slots))
         t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
         o = _lib.tensor_out(out, _lib.tensor_shape(t, len(slots)), dtype, self.cfg.device)
-        check(lib().mp2vg_tensor_slots(self.h, slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(slots),
-                                       ctypes.byref(t), ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()),
-              "tensor_slots")
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        check(lib().mp2vg_tensor_slots_fields(self.h, slots.ctypes.data_as(i32p),
+                                              None if modes is None else modes.ctypes.data_as(i32p), len(slots),
+                                              ctypes.byref(t), ctypes.c_void_p(o.data_ptr()),
+                                              o.numel() * o.element_size()), "tensor_slots_fields")
         if sync:
             self.synchronize()
         return o
@@ -424,15 +436,43 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
         return out
 
 
+def field_plan(display, flags, fields):
+    """(slots, modes) of decode_tensor's `fields`: the display-order slot list, each picture once or
+    ("both") twice, and the MP2VG_FIELD_* mode of each entry (None: no list)."""
+    display = np.asarray(display, np.int32)
+    if fields is None:
+        return display, None
+    if fields in ("weave", "top", "bottom"):
+        return display, np.full(len(display), _lib.FIELDS[fields], np.int32)
+    if fields not in ("first", "both"):
+        raise ValueError(f"fields {fields!r}: expected None, 'weave', 'top', 'bottom', 'first' or 'both'")
+    fl = np.asarray(flags, np.uint32)[display]
+    progressive = (fl & _lib.PIC_PROGRESSIVE_FRAME) != 0
+    tff = (fl & _lib.PIC_TOP_FIELD_FIRST) != 0
+    first = np.where(progressive, _lib.FIELD_PROGRESSIVE, np.where(tff, _lib.FIELD_TOP, _lib.FIELD_BOTTOM))
+    if fields == "first":
+        return display, first.astype(np.int32)
+    second = np.where(progressive, _lib.FIELD_PROGRESSIVE, np.where(tff, _lib.FIELD_BOTTOM, _lib.FIELD_TOP))
+    return np.repeat(display, 2), np.stack([first, second], axis=1).ravel().astype(np.int32)
+
+
 def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
-                  layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False):
+                  layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False, fields=None):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
     dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
     horizontal_size_value x vertical_size_value at the top left when these are set and no larger
     than the coded size, else the coded frame; matrix=None takes the stream's matrix_coefficients.
     A stream without pictures gives an empty tensor, and one of more than 65535 pictures is
-    exported in several calls.  device_parse as in decode_rgb."""
+    exported in several calls.  device_parse as in decode_rgb.
+
+    fields (include/mp2vg.h "Field modes"): None exports every picture as a progressive frame;
+    "weave", "top" or "bottom" that mode for every picture; "first" a progressive frame for pictures
+    with progressive_frame = 1 and else the picture's first field (the top field if
+    top_field_first, else the bottom one), n frames; "both" 2n frames in temporal order: an
+    interlaced picture gives its first field, then its second, a progressive picture its frame
+    twice.  repeat_first_field (3:2 pulldown) is reported in Parsed.flags but ignored here: no
+    field is repeated."""
     parsed = (Scan if device_parse else Parsed)(es, width, height, chroma_format)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
@@ -440,8 +480,9 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
         crop = (0, 0, w, h)
     if matrix is None:
         matrix = export_matrix(parsed.headers)
+    slots, modes = field_plan(parsed.display, parsed.flags, fields)
     t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
-    out = _lib.tensor_out(None, _lib.tensor_shape(t, parsed.npics), dtype, device)
+    out = _lib.tensor_out(None, _lib.tensor_shape(t, len(slots)), dtype, device)
     if not parsed.npics:
         return out
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
@@ -450,10 +491,11 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
         else:
             ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
         ctx.decode()
-        for i in range(0, parsed.npics, EXPORT_MAX_FRAMES):  # mp2vg_tensor_slots takes 65535 per call
-            part = parsed.display[i:i + EXPORT_MAX_FRAMES]
+        for i in range(0, len(slots), EXPORT_MAX_FRAMES):  # mp2vg_tensor_slots_fields takes 65535 per call
+            part = slots[i:i + EXPORT_MAX_FRAMES]
             ctx.export_tensor(part, size, crop=crop, dtype=dtype, mean=mean, std=std, layout=layout, chroma=chroma,
-                              matrix=matrix, out=out[i:i + len(part)], sync=False)
+                              matrix=matrix, out=out[i:i + len(part)], sync=False,
+                              fields=None if modes is None else modes[i:i + len(part)])
         ctx.synchronize()
         return out
 

@@ -17,8 +17,15 @@ own weights; the largest difference is reported in 8-bit steps).  The kernel's s
 LDS / memory instruction counts, VGPRs and LDS bytes are read from the gfx950 ISA of tensor.hip.
 Writes tensor.json and tensor.md into --out.
 
+Field modes (mp2vg_tensor_slots_fields): the 224 x 224 export again with every frame PROGRESSIVE, TOP
+and WEAVE, alternated the same way, and the static figures of the field-mode kernel.  --ab ROOT
+compares the PROGRESSIVE 224 x 224 figure with another checkout's (the parent commit, built): worker
+processes of the two trees alternate on the same stream, each reports its median, and the margin is
+the spread of the other checkout's own medians.
+
     python tools/tensor_bench.py --out profiles/export        # on an MI355X
     python tools/tensor_bench.py --isa-only                   # the ISA figures alone, no GPU
+    python tools/tensor_bench.py --ab ../parent-checkout      # adds the A/B section
 """
 import argparse
 import ctypes
@@ -37,11 +44,14 @@ sys.path.insert(0, REPO)
 W, H, CODED_H, CF, SLOTS = 1920, 1080, 1088, 1, 256
 SIZES = [(224, 224), (640, 360)]
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-KERNEL = "tensor_kernelILi1ELb1ELb0ELi1EE"  # 4:2:0, LINEAR, planar, F16
+KERNEL = "tensor_kernelILi1ELb1ELb0ELi1ELb0EE"  # 4:2:0, LINEAR, planar, F16, without field modes
+KERNEL_FIELDS = "tensor_kernelILi1ELb1ELb0ELi1ELb1EE"  # the same with the field row walk
+FIELD_MODES = ("progressive", "top", "weave")
+AB_ROUNDS = 4
 
 
-def isa_figures():
-    """Static figures of the measured kernel variant from the gfx950 ISA."""
+def isa_figures(kernel=KERNEL):
+    """Static figures of one kernel variant from the gfx950 ISA."""
     from tiny_mp2v_dec_amd import build as B
     csrc = os.path.join(REPO, "tiny_mp2v_dec_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
@@ -50,9 +60,9 @@ def isa_figures():
                                "-I", os.path.join(REPO, "include"), "--offload-device-only", "-S",
                                os.path.join(csrc, "tensor.hip"), "-o", asm], stderr=subprocess.DEVNULL)
         text = open(asm).read()
-    m = re.search(r"^(_ZN\w*%s\w*):[^\n]*\n(.*?)^\.Lfunc_end" % KERNEL, text, re.S | re.M)
+    m = re.search(r"^(_ZN\w*%s\w*):[^\n]*\n(.*?)^\.Lfunc_end" % kernel, text, re.S | re.M)
     if not m:
-        raise RuntimeError(f"kernel {KERNEL} not found in the ISA")
+        raise RuntimeError(f"kernel {kernel} not found in the ISA")
     name, body = m.group(1), m.group(2)
     cls = {"valu": 0, "salu": 0, "lds": 0, "vmem_load": 0, "vmem_store": 0, "other": 0}
     for op in re.findall(r"^\s+([a-z][a-z0-9_]+)\b", body, re.M):
@@ -142,10 +152,127 @@ def measure(reps, warmup):
                          "frames_per_s": round(SLOTS / (f_ms * 1e-3)),
                          "max_abs_diff_8bit_steps": round(float(diff.max()), 3)})
             del fused_out, keep
-    return rows
+        field_rows = measure_fields(ctx, slots, reps, warmup)
+    return rows, field_rows
 
 
-def write_md(path, rows, isa, device):
+def measure_fields(ctx, slots, reps, warmup):
+    """The 224 x 224 export of the same slots with one field mode for every frame, modes alternated."""
+    import torch
+    ow, oh = SIZES[0]
+    out = torch.empty((SLOTS, 3, oh, ow), dtype=torch.float16, device="cuda")
+    torch.cuda.synchronize()
+
+    def run(mode):
+        t0 = time.perf_counter()
+        ctx.export_tensor(slots, (ow, oh), crop=(0, 0, W, H), dtype=torch.float16, mean=MEAN, std=STD, out=out,
+                          sync=True, fields=mode)
+        return time.perf_counter() - t0
+
+    for _ in range(warmup):
+        for mode in FIELD_MODES:
+            run(mode)
+    t = {mode: [] for mode in FIELD_MODES}
+    for _ in range(reps):
+        for mode in FIELD_MODES:
+            t[mode].append(run(mode))
+    return [{"mode": mode, "out": [ow, oh], "reps": reps, "ms": round(statistics.median(t[mode]) * 1e3, 4),
+             "ms_min": round(min(t[mode]) * 1e3, 4), "ms_max": round(max(t[mode]) * 1e3, 4)} for mode in FIELD_MODES]
+
+
+def fused_worker(root, stream, reps, warmup):
+    """One process of the A/B: the package of the checkout at `root`, the stream file, the fused
+    224 x 224 export without field modes; prints its median, minimum and maximum (ms)."""
+    sys.path.insert(0, root)
+    import torch
+    from tiny_mp2v_dec_amd import records as R
+    es = open(stream, "rb").read()
+    parsed = R.Parsed(es, W, CODED_H, CF)
+    ow, oh = SIZES[0]
+    with R.DeviceContext(W, CODED_H, CF, slots=SLOTS) as ctx:
+        ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        ctx.decode()
+        ctx.synchronize()
+        out = torch.empty((SLOTS, 3, oh, ow), dtype=torch.float16, device="cuda")
+        torch.cuda.synchronize()
+        t = []
+        for i in range(warmup + reps):
+            t0 = time.perf_counter()
+            ctx.export_tensor(parsed.display, (ow, oh), crop=(0, 0, W, H), dtype=torch.float16, mean=MEAN, std=STD,
+                              out=out, sync=True)
+            if i >= warmup:
+                t.append(time.perf_counter() - t0)
+    print(json.dumps({"ms": round(statistics.median(t) * 1e3, 4), "ms_min": round(min(t) * 1e3, 4),
+                      "ms_max": round(max(t) * 1e3, 4)}))
+
+
+def ab(parent_root, reps, warmup):
+    """Worker processes of the other checkout and of this one, alternated on one stream; a worker
+    that fails ends the comparison (nothing more is started)."""
+    from tiny_mp2v_dec_amd import records as R
+    es = R.generate_es(width=W, height=CODED_H, chroma_format=CF, n_gops=SLOTS // 16, gop_n=16, gop_m=4, seed=5)
+    runs = {"parent": [], "this": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        stream = os.path.join(tmp, "stream.m2v")
+        with open(stream, "wb") as f:
+            f.write(es)
+        pair = (("parent", os.path.abspath(parent_root)), ("this", REPO))
+        for k in range(AB_ROUNDS):
+            for who, root in (pair if k % 2 == 0 else pair[::-1]):  # parent, this; this, parent; ...
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--fused-worker", root, stream, "--reps",
+                                    str(reps), "--warmup", str(warmup)], capture_output=True, text=True, timeout=300)
+                if r.returncode != 0:
+                    sys.exit(f"tensor_bench --ab: the {who} worker failed ({r.returncode}):\n{r.stderr[-2000:]}")
+                runs[who].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    med = {who: [x["ms"] for x in runs[who]] for who in runs}
+    spread = max(med["parent"]) - min(med["parent"])
+    delta = statistics.median(med["this"]) - statistics.median(med["parent"])
+    return {"out": list(SIZES[0]), "reps": reps, "rounds": AB_ROUNDS, "parent_ms": med["parent"], "this_ms": med["this"],
+            "parent_spread_ms": round(spread, 4), "delta_ms": round(delta, 4), "within_spread": delta <= spread}
+
+
+def field_lines(field_rows, isa_fields, ab_result):
+    lines = ["", "## Field modes", "",
+             "`mp2vg_tensor_slots_fields`, the 224 x 224 export of the same 256 slots with one field mode for",
+             "every frame, the modes alternated in one process (same clock and method as above).  A launch",
+             "whose modes are all PROGRESSIVE runs the kernel without field modes, whose gfx950 instruction",
+             "stream is the one from before the field modes existed; any other launch runs the field-mode",
+             "kernel for all its frames.  TOP and BOTTOM convert only their field's lines (about half the",
+             "rows) and add one rounded average per interpolated row; WEAVE converts every row, as",
+             "PROGRESSIVE does, with the chroma taps of its own field.", ""]
+    if field_rows:
+        lines += ["| mode | ms (min .. max) | against PROGRESSIVE |", "|---|---|---|"]
+        base = field_rows[0]["ms"]
+        for r in field_rows:
+            lines.append(f"| {r['mode'].upper()} | {r['ms']:.3f} ({r['ms_min']:.3f} .. {r['ms_max']:.3f}) | "
+                         f"{r['ms'] / base:.2f} |")
+        top = next(r for r in field_rows if r["mode"] == "top")
+        if top["ms"] > base:
+            lines += ["", "TOP is slower than PROGRESSIVE in this run although it converts half the rows; the cause was",
+                      "not profiled."]
+    else:
+        lines.append("Not measured (no GPU in this run).  Static figures only.")
+    lines += ["", f"Static figures of `{KERNEL_FIELDS}` (the same variant with field modes): VGPRs "
+              f"{isa_fields['vgprs']}, LDS {isa_fields['lds_bytes']} B per workgroup, scratch "
+              f"{isa_fields['scratch_bytes']} B; instructions: VALU {isa_fields['valu']}, SALU {isa_fields['salu']}, "
+              f"LDS {isa_fields['lds']}, global loads {isa_fields['vmem_load']}, global stores "
+              f"{isa_fields['vmem_store']}.  The LDS sets 6 waves per SIMD; up to 80 VGPRs keep that."]
+    if ab_result:
+        a = ab_result
+        lines += ["", "### PROGRESSIVE against the parent commit", "",
+                  f"`--ab`: {a['rounds']} worker processes of the parent commit's checkout and {a['rounds']} of this",
+                  "one, alternated (the order swapped every round) on one box and one stream, each the median of "
+                  f"{a['reps']} fused 224 x 224 exports without field modes.", "",
+                  "| checkout | medians of the runs, ms |", "|---|---|",
+                  "| parent | " + ", ".join(f"{v:.3f}" for v in a["parent_ms"]) + " |",
+                  "| this | " + ", ".join(f"{v:.3f}" for v in a["this_ms"]) + " |", "",
+                  f"Margin = the spread of the parent's own medians: {a['parent_spread_ms']:.3f} ms.  Median of this "
+                  f"checkout's medians minus the parent's: {a['delta_ms']:+.3f} ms: "
+                  + ("inside the margin." if a["within_spread"] else "OUTSIDE the margin.")]
+    return lines
+
+
+def write_md(path, rows, isa, device, field_rows=None, isa_fields=None, ab_result=None):
     lines = ["# Tensor export: fused kernel against the unfused path", "",
              "Written by `tools/tensor_bench.py`.  1080p 4:2:0, 256 slots filled by a generated stream; the",
              "visible 1920 x 1080 of each to float16 NCHW with ImageNet mean / std, LINEAR chroma.  Host",
@@ -190,6 +317,8 @@ def write_md(path, rows, isa, device):
               "row per workgroup 1.477 / 1.687 ms; two rows per workgroup with each lane looping over its own",
               "tap count in the horizontal pass 1.240 / 1.701 ms (now every lane runs the axis' longest count",
               "over zero-padded weights, which keeps several tap loads in flight)."]
+    if isa_fields:
+        lines += field_lines(field_rows, isa_fields, ab_result)
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
 
@@ -200,25 +329,35 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--isa-only", action="store_true")
+    ap.add_argument("--ab", metavar="ROOT", help="a built checkout of the parent commit to compare PROGRESSIVE with")
+    ap.add_argument("--fused-worker", nargs=2, metavar=("ROOT", "STREAM"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.reps < 20:
         ap.error("--reps must be at least 20")
-    isa = isa_figures()
-    rows, device = [], None
+    if a.fused_worker:
+        return fused_worker(a.fused_worker[0], a.fused_worker[1], a.reps, a.warmup)
+    isa, isa_fields = isa_figures(), isa_figures(KERNEL_FIELDS)
+    rows, field_rows, ab_result, device = [], [], None, None
     if not a.isa_only:
         import torch
         if not torch.cuda.is_available():
             sys.exit("tensor_bench: no GPU (a measurement does not fall back; --isa-only gives the static figures)")
         device = torch.cuda.get_device_name(0)
-        rows = measure(a.reps, a.warmup)
+        rows, field_rows = measure(a.reps, a.warmup)
+        if a.ab:
+            ab_result = ab(a.ab, a.reps, a.warmup)
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "tensor.json"), "w") as f:
-        json.dump({"device": device, "rows": rows, "isa": isa}, f, indent=1)
+        json.dump({"device": device, "rows": rows, "isa": isa, "field_rows": field_rows, "isa_fields": isa_fields,
+                   "ab": ab_result}, f, indent=1)
         f.write("\n")
-    write_md(os.path.join(a.out, "tensor.md"), rows, isa, device)
-    for r in rows:
+    write_md(os.path.join(a.out, "tensor.md"), rows, isa, device, field_rows, isa_fields, ab_result)
+    for r in rows + field_rows:
         print(json.dumps(r))
     print(json.dumps(isa))
+    print(json.dumps(isa_fields))
+    if ab_result:
+        print(json.dumps(ab_result))
 
 
 if __name__ == "__main__":
