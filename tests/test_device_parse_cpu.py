@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import parse_mutants as PM
 from conftest import load_manifest, read_stream
 from tiny_mp2v_dec_amd import _lib
 from tiny_mp2v_dec_amd.records import Parsed, Scan, generate_es
@@ -19,34 +20,7 @@ def _geom(e):
     return e["width"], e["height"], e["chroma_format"]
 
 
-def _host(es, w, h, cf):
-    """(status, message, Parsed or None) of the host emitter; one thread, so that the slice blamed
-    for a doubly covered row is the second one in stream order, as in the scan."""
-    try:
-        return 0, "", Parsed(es, w, h, cf, threads=1)
-    except _lib.Mp2vgError as e:
-        return e.status, str(e), None
-
-
-def _twin(es, w, h, cf):
-    """(status, message, (mbs, coefs) or None, rejected by the scan itself)"""
-    try:
-        sc = Scan(es, w, h, cf)
-    except _lib.Mp2vgError as e:
-        return e.status, str(e), None, True
-    try:
-        return 0, "", sc.parse_host(), False
-    except _lib.Mp2vgError as e:
-        return e.status, str(e), None, False
-
-
-def _detail(msg):
-    """the library's own message: the text inside the outer parentheses of Mp2vgError"""
-    return msg.split("(", 1)[1][:-1] if "(" in msg else msg
-
-
-def _same_records(p, rec):
-    return rec[0].tobytes() == p.mbs.tobytes() and rec[1].tobytes() == p.coefs.tobytes()
+_host, _twin, _detail, _same_records = PM.host, PM.twin, PM.detail, PM.same_records
 
 
 @pytest.mark.parametrize("entry", MANIFEST, ids=[e["name"] for e in MANIFEST])
@@ -101,20 +75,7 @@ def test_twin_equals_host_on_a_generator_sweep(seed):
 
 
 # ---- rejections -----------------------------------------------------------------------------
-def _start_codes(es, code):
-    out, i = [], es.find(b"\x00\x00\x01" + bytes([code]))
-    while i >= 0:
-        out.append(i)
-        i = es.find(b"\x00\x00\x01" + bytes([code]), i + 1)
-    return out
-
-
-def _set_bit(es, byte_off, bit, value):
-    b = bytearray(es)
-    pos = byte_off * 8 + bit
-    mask = 0x80 >> (pos % 8)
-    b[pos // 8] = (b[pos // 8] | mask) if value else (b[pos // 8] & ~mask & 0xFF)
-    return bytes(b)
+_start_codes = PM.start_codes
 
 
 def _gen(**kw):
@@ -151,9 +112,7 @@ def test_scan_rejects_an_uncovered_row():
 
 
 def test_twin_rejects_intra_vlc_format_zero():
-    es = generate_es(width=176, height=144, n_gops=1, gop_n=2, gop_m=1, leading_b=0, mix=1)
-    for o in [o + 4 for o in _start_codes(es, 0xB5) if (es[o + 4] >> 4) == 8]:
-        es = _set_bit(es, o, 28, 0)
+    es = PM.vlc0_stream()[0]
     _check_same_rejection(es, -2, "intra_vlc_format=0")
 
 
@@ -169,19 +128,7 @@ def test_twin_rejects_a_truncated_last_slice():
     assert ts == hs and _detail(tm) == _detail(hm)
 
 
-SLICE_REASONS = [
-    "macroblock beyond the end of the row", "bad macroblock_address_increment", "slice does not start at column 0",
-    "skipped macroblock in an I picture", "skip run beyond the end of the row",
-    "skipped MB reads outside the reference", "bad macroblock_type", "dual-prime prediction",
-    "reserved frame_motion_type", "4:4:4 field DCT", "bad motion_code", "prediction from a missing reference",
-    "motion vector reads outside the reference", "bad coded_block_pattern",
-    "bad DCT coefficient code", "coefficient run past position 63",
-    "slice does not cover the whole macroblock row",
-]
-# Not in the list: "bad dct_dc_size" cannot happen (B.12 and B.13 are complete prefix codes: every
-# 9- / 10-bit window decodes), "intra_vlc_format=0" and the truncated slice have their own streams
-# above, and "slice overruns the buffer" needs a macroblock that ends more than 8 bytes past its
-# slice without meeting any other error first, which no mutant here does.
+SLICE_REASONS = PM.SLICE_REASONS  # (and why four reasons are not in the list)
 
 
 @pytest.fixture(scope="module")
@@ -191,25 +138,11 @@ def mutants():
     records equal when both accept).  Byte mutations inside one slice give one failing slice, so
     status and message must agree exactly unless the scan itself rejected."""
     out = []
-    streams = [
-        (generate_es(width=176, height=48, chroma_format=1, n_gops=1, gop_n=6, gop_m=3, seed=7,
-                     frame_pred_frame_dct=0, f_code=2), 176, 48, 1),
-        (generate_es(width=64, height=48, chroma_format=3, n_gops=1, gop_n=6, gop_m=3, seed=8,
-                     frame_pred_frame_dct=0, f_code=3, escape_permille=200), 64, 48, 3),
-        (generate_es(width=80, height=48, chroma_format=2, n_gops=1, gop_n=4, gop_m=1, seed=9, leading_b=0,
-                     frame_pred_frame_dct=0, f_code=1), 80, 48, 2),
-        (generate_es(width=176, height=48, chroma_format=1, n_gops=1, gop_n=3, gop_m=1, seed=10, leading_b=0,
-                     mix=1), 176, 48, 1),
-    ]
-    for si, (es, w, h, cf) in enumerate(streams):
-        rng = np.random.default_rng(1000 + si)
-        first_slice = es.find(b"\x00\x00\x01\x01")
-        for _ in range(900):
-            b = bytearray(es)
-            pos = int(rng.integers(first_slice + 4, len(b)))
-            b[pos] = int(rng.integers(0, 256))
-            hs, hm, p = _host(bytes(b), w, h, cf)
-            ts, tm, rec, by_scan = _twin(bytes(b), w, h, cf)
+    for si, (es, w, h, cf) in enumerate(PM.base_streams()):
+        for pos, val in PM.walk(si, es):
+            b = PM.mutate(es, pos, val)
+            hs, hm, p = _host(b, w, h, cf)
+            ts, tm, rec, by_scan = _twin(b, w, h, cf)
             same = _same_records(p, rec) if hs == 0 and ts == 0 else None
             out.append((hs, hm, ts, tm, by_scan, same))
     return out

@@ -6,6 +6,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import parse_mutants as PM
 from conftest import load_manifest, read_stream
 from helpers import oracle_frames, yuv_md5
 from tiny_mp2v_dec_amd import _lib
@@ -92,12 +93,15 @@ def test_generated_streams_vs_oracle(kw):
     _assert_frames_equal(frames, oracle_frames(parsed))
 
 
-def test_reader_tail_last_slice_ends_at_the_last_byte():
+@pytest.mark.parametrize("seed", PM.TAIL_SEEDS)
+def test_reader_tail_last_slice_ends_at_the_last_byte(seed):
     """no sequence_end_code after the last slice: its last byte is the buffer's last byte, and the
-    reader's refills run into the pad"""
-    es = R.generate_es(width=64, height=32, n_gops=1, gop_n=4, gop_m=1, leading_b=0, seed=5)
-    assert es.endswith(b"\x00\x00\x01\xb7")
-    es = es[:-4]
+    reader's refills run into the pad.  The four streams' uploaded spans are 0, 1, 2 and 3 bytes
+    past a multiple of 4 long, so the hand-over from aligned loads to the byte-wise tail is met at
+    each distance from the hard end."""
+    assert sorted(PM.tail_span(PM.tail_stream(s)) % 4 for s in PM.TAIL_SEEDS) == [0, 1, 2, 3]
+    es = PM.tail_stream(seed)  # (asserts the end code before it strips it)
+    assert not es.endswith(b"\x00\x00\x01\xb7")
     parsed, frames, (mbs, coefs), _ = _device_decode(es, 64, 32, 1)
     assert mbs.tobytes() == parsed.mbs.tobytes() and coefs.tobytes() == parsed.coefs.tobytes()
     _assert_frames_equal(frames, oracle_frames(parsed))
