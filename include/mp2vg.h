@@ -170,6 +170,38 @@ int  mp2vg_batch_validate(const mp2vg_config_t* cfg, int32_t nslots, const mp2vg
                           int32_t npics, const mp2vg_mb_t* mbs, uint64_t nmbs,
                           const uint32_t* coefs, uint64_t ncoefs, int32_t* nlaunches,
                           int32_t* launch_of_pic, int32_t* launch_mode, int32_t max_launches);
+/* The whole plan of a batch, host only: what mp2vg_batch_upload would make resident for
+ * mp2vg_batch_decode (the same validation and planning as mp2vg_batch_validate, on the same
+ * device-less context).  Every array is the caller's, sized by its max_* field (NULL or 0: counts
+ * only); every n* field returns the plan's true count, and entries past max_* are not written.
+ *   slices    4 words per slice, in launch order: index of its picture in the batch, first MB
+ *             record, MB records, flag bits (bit 0: stores its anchor tiles in the loop, bit 1:
+ *             one-direction B picture, bit 2: that direction is backward)
+ *   launches  6 words per launch, in enqueue order per set: first slice, end slice, kernel mode
+ *             (mp2vg_batch_validate), dependency level, picture set (= stream), slices per
+ *             workgroup (0: one)
+ *   writes    2 words per picture in decode order: destination slot, 1 when the batch leaves its
+ *             anchor tiles current
+ *   ext_reads 2 words per slot read before the batch writes it: slot, reading set
+ *   post      2 words per tile conversion that follows a launch: launch, slot
+ *   foot      2 words per slot of each set's footprint: set, slot (what the next batch's sets
+ *             wait for)
+ * Returns MP2VG_OK, or MP2VG_E_INVALID with the reason in mp2vg_last_error(). */
+typedef struct mp2vg_plan {
+    uint32_t* slices;
+    int32_t*  launches;
+    int32_t*  writes;
+    int32_t*  ext_reads;
+    int32_t*  post;
+    int32_t*  foot;
+    int32_t   max_slices, max_launches, max_writes, max_ext_reads, max_post, max_foot;
+    int32_t   nslices, nlaunches, nwrites, next_reads, npost, nfoot;
+    int32_t   nsets;      /* picture sets of the batch */
+    int32_t   reserved;
+} mp2vg_plan_t;
+int  mp2vg_batch_plan(const mp2vg_config_t* cfg, int32_t nslots, const mp2vg_picture_t* pics,
+                      int32_t npics, const mp2vg_mb_t* mbs, uint64_t nmbs,
+                      const uint32_t* coefs, uint64_t ncoefs, mp2vg_plan_t* plan);
 /* Enqueue the reconstruct of every picture of the resident batch: pictures are grouped by
  * reference-dependency depth and each depth level is one kernel launch (one workgroup per
  * slice = MB row).  Asynchronous; per-launch device times are recorded with HIP events. */

@@ -4,9 +4,9 @@ import numpy as np
 import pytest
 
 from conftest import load_manifest, read_stream
-from helpers import oracle_frames, yuv_md5
+from helpers import _inside, fill_mb, oracle_frames, yuv_md5  # noqa: F401  (_inside: re-exported)
 from tiny_mp2v_dec_amd import records as R
-from tiny_mp2v_dec_amd._lib import MB_BWD, MB_DCT_FIELD, MB_FIELD_MC, MB_FWD, MB_INTRA, COEF_DC, COEF_FIRST1S
+from tiny_mp2v_dec_amd._lib import MB_BWD, MB_FWD, MB_INTRA, COEF_DC
 
 pytestmark = pytest.mark.gpu
 
@@ -54,85 +54,9 @@ def random_batch(width, height, cf, npics, seed, field=True, big=False, n_intra=
         for k in range(n):
             m = mbs[p * n + k]
             m["x"], m["y"] = k % mbw, k // mbw
-            m["qscale"] = rng.integers(1, 113)
-            intra = p < n_intra or rng.random() < 0.1
-            flags = 0
-            if intra:
-                flags |= MB_INTRA
-                cbp = (1 << nb) - 1
-            else:
-                d = rng.integers(0, 3) if p > n_intra else 0
-                flags |= [MB_FWD, MB_BWD, MB_FWD | MB_BWD][d]
-                fld = field and rng.random() < 0.3
-                if fld:
-                    flags |= MB_FIELD_MC
-                    for r in range(2):
-                        for s in range(2):
-                            if rng.random() < 0.5:
-                                flags |= 1 << (8 + 2 * r + s)
-                # vectors that keep every read inside every plane
-                for r in range(2 if fld else 1):
-                    for s in range(2):
-                        for _ in range(20):
-                            mx, my = rng.integers(-40, 40), rng.integers(-40, 40)
-                            if _inside(width, height, cf, m["x"], m["y"], mx, my, fld, (flags >> (8 + 2 * r + s)) & 1):
-                                break
-                        else:
-                            mx, my = 0, 0
-                            if fld:
-                                flags &= ~(1 << (8 + 2 * r + s))
-                                flags |= r << (8 + 2 * r + s)
-                        m["mv"][r, s] = (mx, my)
-                cbp = int(rng.integers(0, 1 << nb)) if rng.random() < 0.7 else 0
-            if cbp and rng.random() < 0.4 and cf != 3:  # 4:4:4 field DCT is refused (test_validate.py)
-                flags |= MB_DCT_FIELD
-            m["flags"], m["cbp"] = flags, cbp
-            m["coef_off"] = len(coefs)
-            for b in range(nb):
-                if not cbp >> b & 1:
-                    continue
-                pos = 0
-                if intra:
-                    coefs.append(R._lib.coef_pack(int(rng.integers(0, 2048)), 0, b, COEF_DC, m["x"]))
-                    pos = 1
-                elif rng.random() < 0.3:
-                    coefs.append(R._lib.coef_pack(int(rng.choice([-1, 1])), 0, b, COEF_FIRST1S, m["x"]))
-                    pos = 1
-                ncoef = int(rng.integers(0 if intra else 1, 20))
-                for _ in range(ncoef):
-                    pos += int(rng.integers(0, 4))
-                    if pos > 63:
-                        break
-                    lvl = int(rng.integers(-2048, 2048)) if (big and rng.random() < 0.3) else int(rng.integers(-40, 41))
-                    coefs.append(R._lib.coef_pack(lvl, pos, b, 0, m["x"]))
-                    pos += 1
-            m["ncoef"] = len(coefs) - m["coef_off"]
+            fill_mb(rng, m, coefs, width, height, cf, p < n_intra,
+                    [MB_FWD, MB_BWD, MB_FWD | MB_BWD] if p > n_intra else [MB_FWD], field, big)
     return pics, mbs, np.array(coefs, dtype=np.uint32)
-
-
-def _inside(width, height, cf, mbx, mby, mvx, mvy, field, fs):
-    pw = [width] + [width if cf == 3 else width // 2] * 2
-    ph = [height] + [height if cf != 1 else height // 2] * 2
-    for plane in range(3):
-        mx, my = mvx, mvy
-        if plane:
-            if cf < 3:
-                mx >>= 1
-            if cf < 2:
-                my >>= 1
-        w = 16 if plane == 0 else (16 if cf == 3 else 8)
-        h = 16 if plane == 0 else (8 if cf == 1 else 16)
-        x0 = mbx * w + (mx >> 1)
-        x1 = x0 + w - 1 + (mx & 1)
-        if not field:
-            y0 = mby * h + (my >> 1)
-            y1 = y0 + h - 1 + (my & 1)
-        else:
-            y0 = mby * h + fs + 2 * (my >> 1)
-            y1 = y0 + 2 * (h // 2 - 1) + 2 * (my & 1)
-        if x0 < 0 or y0 < 0 or x1 > pw[plane] - 1 or y1 > ph[plane] - 1:
-            return False
-    return True
 
 
 class _P:  # minimal Parsed-like holder for oracle_frames

@@ -108,6 +108,14 @@ class Export(ctypes.Structure):  # mp2vg_export_t
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
+class Plan(ctypes.Structure):  # mp2vg_plan_t
+    _fields_ = [("slices", ctypes.POINTER(ctypes.c_uint32))] + [
+        (n, ctypes.POINTER(ctypes.c_int32)) for n in ("launches", "writes", "ext_reads", "post", "foot")] + [
+        (n, ctypes.c_int32) for n in (
+            "max_slices", "max_launches", "max_writes", "max_ext_reads", "max_post", "max_foot",
+            "nslices", "nlaunches", "nwrites", "next_reads", "npost", "nfoot", "nsets", "reserved")]
+
+
 EXPORT_RGB_PLANAR, EXPORT_RGB_PACKED = 0, 1
 EXPORT_CHROMA_NEAREST, EXPORT_CHROMA_LINEAR = 0, 1
 
@@ -132,7 +140,7 @@ RENDER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(Frame))
 # every symbol declared in include/mp2vg.h
 EXPORTS = [
     "mp2vg_abi_version", "mp2vg_status_string", "mp2vg_last_error", "mp2vg_create", "mp2vg_destroy",
-    "mp2vg_frame_geometry", "mp2vg_reserve_slots", "mp2vg_batch_upload", "mp2vg_batch_validate", "mp2vg_batch_decode",
+    "mp2vg_frame_geometry", "mp2vg_reserve_slots", "mp2vg_batch_upload", "mp2vg_batch_validate", "mp2vg_batch_plan", "mp2vg_batch_decode",
     "mp2vg_synchronize", "mp2vg_last_launch_times", "mp2vg_last_batch_time", "mp2vg_batch_times", "mp2vg_batches_span", "mp2vg_download_slot", "mp2vg_copy_slot_packed", "mp2vg_slot_device_ptr", "mp2vg_sink_device_ptr", "mp2vg_clock_probe", "mp2vg_pool_probe", "mp2vg_pool_placement", "mp2vg_cpu_budget", "mp2vg_invalidate_slot",
     "mp2vg_slot_digests", "mp2vg_parse_es", "mp2vg_parsed_counts", "mp2vg_parsed_pictures", "mp2vg_parsed_mbs",
     "mp2vg_parsed_coefs", "mp2vg_parsed_display_order", "mp2vg_parsed_gop_index", "mp2vg_parsed_stream_headers",
@@ -174,6 +182,7 @@ def lib():
         "mp2vg_batch_upload": ([VP, VP, I32, VP, U64, VP, U64], ctypes.c_int),
         "mp2vg_batch_validate": ([P(Config), I32, VP, I32, VP, U64, VP, U64, P(I32), P(I32), P(I32), I32],
                                  ctypes.c_int),
+        "mp2vg_batch_plan": ([P(Config), I32, VP, I32, VP, U64, VP, U64, P(Plan)], ctypes.c_int),
         "mp2vg_batch_decode": ([VP], ctypes.c_int),
         "mp2vg_synchronize": ([VP], ctypes.c_int),
         "mp2vg_last_launch_times": ([VP, P(ctypes.c_float), I32, P(I32)], ctypes.c_int),

@@ -1142,18 +1142,64 @@ extern "C" int mp2vg_batch_download_records(mp2vg_ctx_t* c, mp2vg_mb_t* mbs, uin
     return MP2VG_OK;
 }
 
+// a host-side shell of a context: plan_batch reads only the geometry, the slot count and the
+// number of picture sets (as mp2vg_create sets them; no device: 256 CUs assumed)
+static void init_shell(mp2vg_ctx_t& shell, const mp2vg_config_t* cfg, int32_t nslots) {
+    shell.cfg = *cfg;
+    shell.g.init(cfg->width, cfg->height, cfg->chroma_format);
+    shell.nslots = nslots;
+    shell.nstreams = default_streams(cfg);
+}
+
+extern "C" int mp2vg_batch_plan(const mp2vg_config_t* cfg, int32_t nslots, const mp2vg_picture_t* pics,
+                                int32_t npics, const mp2vg_mb_t* mbs, uint64_t nmbs, const uint32_t* coefs,
+                                uint64_t ncoefs, mp2vg_plan_t* out) {
+    if (!cfg || nslots <= 0 || !pics || npics <= 0 || !mbs || (!coefs && ncoefs) || !out) return MP2VG_E_INVALID;
+    if (mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
+    mp2vg_ctx_t shell;
+    init_shell(shell, cfg, nslots);
+    // the call batch_upload makes (untrusted records), with every output it keeps in the bank
+    std::vector<SliceDesc> slices;
+    std::vector<Launch> lb;
+    std::vector<std::vector<int32_t>> foot;
+    TilePlan tplan;
+    const int rc = plan_batch(&shell, pics, npics, mbs, nmbs, coefs, ncoefs, slices, lb, &foot, false, &tplan);
+    if (rc != MP2VG_OK) return rc;
+    auto room = [](const void* p, int32_t i, int32_t max) { return p && i < max; };
+    out->nslices = (int32_t)slices.size();
+    for (int32_t i = 0; i < out->nslices && room(out->slices, i, out->max_slices); i++) {
+        const uint32_t w[4] = {slices[i].pic, slices[i].mb_begin, slices[i].mb_count, slices[i].reserved};
+        memcpy(out->slices + 4 * (size_t)i, w, sizeof w);
+    }
+    out->nlaunches = (int32_t)lb.size();
+    for (int32_t i = 0; i < out->nlaunches && room(out->launches, i, out->max_launches); i++) {
+        const int32_t w[6] = {(int32_t)lb[i].begin, (int32_t)lb[i].end, lb[i].mcm, lb[i].level, lb[i].set, lb[i].mates};
+        memcpy(out->launches + 6 * (size_t)i, w, sizeof w);
+    }
+    auto pairs = [&](const std::vector<std::pair<int32_t, int32_t>>& v, int32_t* dst, int32_t max, int32_t* n) {
+        *n = (int32_t)v.size();
+        for (int32_t i = 0; i < *n && room(dst, i, max); i++) dst[2 * (size_t)i] = v[i].first, dst[2 * (size_t)i + 1] = v[i].second;
+    };
+    std::vector<std::pair<int32_t, int32_t>> wr, ft;
+    for (const auto& w : tplan.writes) wr.push_back({w.first, (int32_t)w.second});
+    for (size_t s = 0; s < foot.size(); s++)
+        for (int32_t x : foot[s]) ft.push_back({(int32_t)s, x});
+    pairs(wr, out->writes, out->max_writes, &out->nwrites);
+    pairs(tplan.ext_reads, out->ext_reads, out->max_ext_reads, &out->next_reads);
+    pairs(tplan.post, out->post, out->max_post, &out->npost);
+    pairs(ft, out->foot, out->max_foot, &out->nfoot);
+    out->nsets = (int32_t)foot.size();
+    return MP2VG_OK;
+}
+
 extern "C" int mp2vg_batch_validate(const mp2vg_config_t* cfg, int32_t nslots, const mp2vg_picture_t* pics,
                                     int32_t npics, const mp2vg_mb_t* mbs, uint64_t nmbs, const uint32_t* coefs,
                                     uint64_t ncoefs, int32_t* nlaunches, int32_t* launch_of_pic,
                                     int32_t* launch_mode, int32_t max_launches) {
     if (!cfg || nslots <= 0 || !pics || npics <= 0 || !mbs || (!coefs && ncoefs)) return MP2VG_E_INVALID;
     if (mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
-    // a host-side shell of a context: plan_batch reads only the geometry and the slot count
     mp2vg_ctx_t shell;
-    shell.cfg = *cfg;
-    shell.g.init(cfg->width, cfg->height, cfg->chroma_format);
-    shell.nslots = nslots;
-    shell.nstreams = default_streams(cfg);
+    init_shell(shell, cfg, nslots);
     std::vector<SliceDesc> slices;
     std::vector<Launch> lb;
     const int rc = plan_batch(&shell, pics, npics, mbs, nmbs, coefs, ncoefs, slices, lb);

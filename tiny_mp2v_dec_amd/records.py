@@ -177,6 +177,43 @@ def plan_batch(width, height, chroma_format, nslots, pics, mbs, coefs, one_strea
     return of_pic, mode[:min(n.value, len(mode))].copy()
 
 
+def plan_dump(width, height, chroma_format, nslots, pics, mbs, coefs, one_stream=False):
+    """mp2vg_batch_plan: the whole plan the upload would make resident, with no device.  A dict of
+    int arrays: slices (n, 4: pic, mb_begin, mb_count, flag bits), launches (n, 6: begin, end,
+    mode, level, set, mates), writes (npics, 2: slot, tiles), ext_reads (n, 2: slot, set), post
+    (n, 2: launch, slot), foot (list of slot arrays, one per set).  Raises Mp2vgError for a batch
+    the upload would refuse."""
+    cfg = _lib.make_config(width, height, chroma_format, pool=nslots,
+                           flags=_lib.MP2VG_CTX_ONE_STREAM if one_stream else 0)
+    pics = np.ascontiguousarray(pics, PIC_DTYPE)
+    mbs = np.ascontiguousarray(mbs, MB_DTYPE)
+    coefs = np.ascontiguousarray(coefs, np.uint32)
+    vp = ctypes.c_void_p
+    plan = _lib.Plan()
+
+    def call():
+        check(lib().mp2vg_batch_plan(ctypes.byref(cfg), nslots, pics.ctypes.data_as(vp), len(pics),
+                                     mbs.ctypes.data_as(vp), len(mbs),
+                                     coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs),
+                                     ctypes.byref(plan)), "batch_plan")
+
+    call()  # counts only
+    width_of = {"slices": 4, "launches": 6, "writes": 2, "ext_reads": 2, "post": 2, "foot": 2}
+    out = {}
+    for name, k in width_of.items():
+        n = getattr(plan, "n" + name if name != "ext_reads" else "next_reads")
+        a = np.zeros((n, k), np.uint32 if name == "slices" else np.int32)
+        out[name] = a
+        setattr(plan, "max_" + name, n)
+        ct = ctypes.c_uint32 if name == "slices" else ctypes.c_int32
+        setattr(plan, name, a.ctypes.data_as(ctypes.POINTER(ct)) if n else None)
+    call()
+    out["slices"] = out["slices"].astype(np.int64)
+    ft = out["foot"]
+    out["foot"] = [ft[ft[:, 0] == s, 1].copy() for s in range(plan.nsets)]
+    return out
+
+
 def validate_batch(width, height, chroma_format, nslots, pics, mbs, coefs):
     """Number of kernel launches of a valid batch (plan_batch); raises Mp2vgError otherwise."""
     return len(plan_batch(width, height, chroma_format, nslots, pics, mbs, coefs)[1])
