@@ -400,7 +400,25 @@ int  mp2vg_export_planes(int32_t device, const uint8_t* const planes[3], const i
  *     rectangle (the rule of the chroma taps).
  * A mode other than PROGRESSIVE needs an even coded height, a multiple of 4 for 4:2:0 (every decoder
  * context has one), else MP2VG_E_INVALID.
- * Out of scope: motion-adaptive deinterlacing, filters other than the triangle, padding. */
+ *
+ * Placement (mp2vg_tensor_slots_placed / mp2vg_tensor_planes_placed): the resized picture fills the
+ * rectangle (dst_x, dst_y, dst_w, dst_h) of the out_w x out_h output (the canvas) and every other
+ * element is a pad colour: letterboxing / pillarboxing in the same launch.  Placement changes steps
+ * 2, 3 and 5 only; step 1 is untouched, so every MP2VG_FIELD_* mode works with it as without.
+ *     Step 2: the tap tables are those of (src_w -> dst_w) and (src_h -> dst_h).
+ *     Step 3: the two passes give Q_img[dst_h][dst_w]; the canvas Q[y][x], 0 <= y < out_h and
+ *             0 <= x < out_w, is Q_img[y - dst_y][x - dst_x] inside the rectangle and 64 pad[c]
+ *             outside it.
+ *     Step 4 runs over the whole canvas unchanged, so a pad element of channel c is pad[c] for U8,
+ *             fmaf((float)pad[c], scale[c], bias[c]) for F32 (no special case) and that value
+ *             rounded to nearest even for F16 / BF16.
+ *     Step 5 is unchanged over the canvas, and so is mp2vg_tensor_bytes.
+ * dst_x, dst_y >= 0, dst_w, dst_h >= 1, dst_x + dst_w <= out_w, dst_y + dst_h <= out_h, the reserved
+ * fields 0, and the ratio rule of step 2 holds for the rectangle (src_w <= 32 dst_w, src_h <= 32
+ * dst_h; out_w and out_h are then not judged by it), else MP2VG_E_INVALID.  A rectangle of four
+ * zeros is the whole output: no placement, pad is never written.  One placement per launch.
+ * Out of scope: motion-adaptive deinterlacing, filters other than the triangle, pad modes other
+ * than a constant colour, a placement per frame of a launch. */
 enum { MP2VG_TENSOR_U8 = 0, MP2VG_TENSOR_F16 = 1, MP2VG_TENSOR_BF16 = 2, MP2VG_TENSOR_F32 = 3 };
 enum { MP2VG_FIELD_PROGRESSIVE = 0, MP2VG_FIELD_TOP = 1, MP2VG_FIELD_BOTTOM = 2, MP2VG_FIELD_WEAVE = 3 };
 #define MP2VG_TENSOR_MAX_TAPS 65
@@ -451,6 +469,44 @@ int  mp2vg_tensor_planes_field(int32_t device, const uint8_t* const planes[3], c
                                int32_t chroma_format, int32_t coded_w, int32_t coded_h, int32_t field,
                                const mp2vg_tensor_t* t, void* dst_device, uint64_t dst_bytes);
 
+/* Placement (the contract is in the block above the enums). */
+typedef struct mp2vg_tensor_place {
+    int32_t dst_x, dst_y, dst_w, dst_h; /* the picture's rectangle inside out_w x out_h; all 0 = the whole output */
+    uint8_t pad[3];                     /* 8-bit R'G'B' of every element outside it */
+    uint8_t reserved0;                  /* must be 0 */
+    int32_t reserved[3];                /* must be 0 */
+} mp2vg_tensor_place_t;                 /* 32 bytes */
+/* mp2vg_tensor_slots_fields / mp2vg_tensor_planes_field with a placement: ordering, staging and
+ * limits as those.  place = NULL (or its rectangle all 0) is the call without a placement bit for
+ * bit, through the same kernels.  Every argument is checked before the first HIP call. */
+int  mp2vg_tensor_slots_placed(mp2vg_ctx_t* ctx, const int32_t* slots, const int32_t* fields, int32_t n,
+                               const mp2vg_tensor_t* t, const mp2vg_tensor_place_t* place,
+                               void* dst_device, uint64_t dst_bytes);
+int  mp2vg_tensor_planes_placed(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                                int32_t chroma_format, int32_t coded_w, int32_t coded_h, int32_t field,
+                                const mp2vg_tensor_t* t, const mp2vg_tensor_place_t* place,
+                                void* dst_device, uint64_t dst_bytes);
+
+/* The rectangles of a placement from the shape the source is shown at (host only, 64-bit integer
+ * arithmetic).  src = (x, y, w, h) is the source rectangle, par_n : par_d the pixel's width :
+ * height (each 1 .. 2^24), so the displayed shape is A : B with A = w par_n, B = h par_d;
+ * rnd(p, q) = floor((2 p + q) / (2 q)).
+ *   MP2VG_FIT_STRETCH: src_out = src, dst_out = (0, 0, out_w, out_h).
+ *   MP2VG_FIT_CONTAIN (letterbox / pillarbox, centred): src_out = src; if A out_h >= B out_w:
+ *       dst_w = out_w, dst_h = clamp(rnd(B out_w, A), 1, out_h), else dst_h = out_h,
+ *       dst_w = clamp(rnd(A out_h, B), 1, out_w); dst_x = (out_w - dst_w) >> 1, dst_y likewise.
+ *   MP2VG_FIT_COVER (the centre crop that fills the output): dst_out = (0, 0, out_w, out_h); if
+ *       A out_h >= B out_w: h kept, w' = clamp(rnd(h par_d out_w, par_n out_h), 1, w),
+ *       x' = x + ((w - w') >> 1), else w kept, h' = clamp(rnd(w par_n out_h, par_d out_w), 1, h),
+ *       y' = y + ((h - h') >> 1).
+ * src_out goes into mp2vg_tensor_t.src_*, dst_out into mp2vg_tensor_place_t.dst_*.
+ * MP2VG_E_INVALID for a mode outside MP2VG_FIT_*, x or y below 0, w, h, out_w or out_h outside
+ * 1 .. 16384, par out of range, or a result whose ratio is above 32 on an axis (the export would
+ * refuse it). */
+enum { MP2VG_FIT_STRETCH = 0, MP2VG_FIT_CONTAIN = 1, MP2VG_FIT_COVER = 2 };
+int  mp2vg_tensor_fit(int32_t mode, const int32_t src[4], int32_t par_n, int32_t par_d,
+                      int32_t out_w, int32_t out_h, int32_t src_out[4], int32_t dst_out[4]);
+
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c
  * (decoder.h:124-130), with the reference's field names (mp2v_hdr.h:61-141) and parsed the way
@@ -499,6 +555,15 @@ typedef struct mp2vg_stream_headers {
  * (BT.709, the assumption of 13818-2 6.3.6) when the extension or the description is absent or
  * the code is 2 ("unspecified"); MP2VG_E_UNSUPPORTED for 0, 3 and codes above 7. */
 int  mp2vg_export_matrix(const mp2vg_stream_headers_t* headers, int32_t* matrix);
+
+/* The pixel aspect par_n : par_d (pixel width : pixel height, reduced) of a stream, for
+ * mp2vg_tensor_fit (13818-2 6.3.3).  aspect_ratio_information 1 is 1:1.  Codes 2, 3 and 4 are the
+ * display aspect ratios dw : dh = 4:3, 16:9 and 221:100 of W x H, which is display_horizontal_size x
+ * display_vertical_size when the sequence display extension is present and both are non-zero, else
+ * horizontal_size_value | horizontal_size_extension << 12 and the height likewise; then par =
+ * (dw H) : (dh W) reduced by their gcd (720 x 576 at 16:9 is 64:45).  MP2VG_E_UNSUPPORTED for code
+ * 0 and codes 5..15; MP2VG_E_INVALID for a size of 0. */
+int  mp2vg_stream_pixel_aspect(const mp2vg_stream_headers_t* headers, int32_t* par_n, int32_t* par_d);
 
 /* ---- host record emitter -------------------------------------------------------------- */
 typedef struct mp2vg_parsed mp2vg_parsed_t;

@@ -127,6 +127,15 @@ class Tensor(ctypes.Structure):  # mp2vg_tensor_t
                 ("reserved", ctypes.c_int32 * 4)]
 
 
+class Place(ctypes.Structure):  # mp2vg_tensor_place_t
+    _fields_ = [("dst_x", ctypes.c_int32), ("dst_y", ctypes.c_int32), ("dst_w", ctypes.c_int32),
+                ("dst_h", ctypes.c_int32), ("pad", ctypes.c_uint8 * 3), ("reserved0", ctypes.c_uint8),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+assert ctypes.sizeof(Place) == 32
+FIT_STRETCH, FIT_CONTAIN, FIT_COVER = 0, 1, 2  # MP2VG_FIT_*
+FITS = {"stretch": FIT_STRETCH, "contain": FIT_CONTAIN, "cover": FIT_COVER}
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 TENSOR_MAX_TAPS = 65
 FIELD_PROGRESSIVE, FIELD_TOP, FIELD_BOTTOM, FIELD_WEAVE = 0, 1, 2, 3  # MP2VG_FIELD_*
@@ -153,6 +162,7 @@ EXPORTS = [
     "mp2vg_export_planes",
     "mp2vg_tensor_weights", "mp2vg_tensor_bytes", "mp2vg_tensor_slots", "mp2vg_tensor_planes",
     "mp2vg_tensor_slots_fields", "mp2vg_tensor_planes_field", "mp2vg_parsed_picture_flags", "mp2vg_scan_picture_flags",
+    "mp2vg_tensor_slots_placed", "mp2vg_tensor_planes_placed", "mp2vg_tensor_fit", "mp2vg_stream_pixel_aspect",
     "mp2vg_scan_es", "mp2vg_scan_counts", "mp2vg_scan_pictures", "mp2vg_scan_display_order",
     "mp2vg_scan_gop_index", "mp2vg_scan_shards", "mp2vg_scan_stream_headers", "mp2vg_scan_free",
     "mp2vg_scan_parse_host", "mp2vg_batch_upload_es", "mp2vg_batch_record_counts",
@@ -232,6 +242,11 @@ def lib():
         "mp2vg_tensor_planes": ([I32, P(VP), P(I32), I32, I32, I32, P(Tensor), VP, U64], ctypes.c_int),
         "mp2vg_tensor_slots_fields": ([VP, P(I32), P(I32), I32, P(Tensor), VP, U64], ctypes.c_int),
         "mp2vg_tensor_planes_field": ([I32, P(VP), P(I32), I32, I32, I32, I32, P(Tensor), VP, U64], ctypes.c_int),
+        "mp2vg_tensor_slots_placed": ([VP, P(I32), P(I32), I32, P(Tensor), P(Place), VP, U64], ctypes.c_int),
+        "mp2vg_tensor_planes_placed": ([I32, P(VP), P(I32), I32, I32, I32, I32, P(Tensor), P(Place), VP, U64],
+                                       ctypes.c_int),
+        "mp2vg_tensor_fit": ([I32, P(I32), I32, I32, I32, I32, P(I32), P(I32)], ctypes.c_int),
+        "mp2vg_stream_pixel_aspect": ([P(StreamHeaders), P(I32), P(I32)], ctypes.c_int),
         "mp2vg_parsed_picture_flags": ([VP, P(ctypes.c_uint32), I32], ctypes.c_int),
         "mp2vg_scan_picture_flags": ([VP, P(ctypes.c_uint32), I32], ctypes.c_int),
         "mp2vg_scan_es": ([VP, U64, P(Config), P(VP)], ctypes.c_int),
@@ -337,6 +352,43 @@ def make_tensor(size, crop=None, dtype="float16", mean=None, std=None, layout="n
     x, y, w, h = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
     return Tensor(e.layout, e.matrix, e.chroma, x, y, w, h, int(size[0]), int(size[1]), TENSOR_DTYPES[name][0],
                   (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias), (ctypes.c_int32 * 4)())
+
+
+def make_place(rect, pad=(0, 0, 0)):
+    """mp2vg_tensor_place_t: rect = (x, y, w, h) of the picture inside the output, pad = the 8-bit
+    (R, G, B) of every element outside it."""
+    x, y, w, h = (int(v) for v in rect)
+    pad = [int(v) for v in pad]
+    if len(pad) != 3 or any(v < 0 or v > 255 for v in pad):
+        raise ValueError(f"pad {pad!r}: expected three values 0..255 (R, G, B)")
+    return Place(x, y, w, h, (ctypes.c_uint8 * 3)(*pad), 0, (ctypes.c_int32 * 3)())
+
+
+def tensor_fit(mode, src, par, size):
+    """(src_out, dst_out) of mp2vg_tensor_fit: mode "stretch" / "contain" / "cover" (or MP2VG_FIT_*),
+    src = (x, y, w, h) the source rectangle, par = (n, d) the pixel's width : height, size =
+    (out_w, out_h).  src_out is the crop to export, dst_out the picture's rectangle in the output."""
+    if isinstance(mode, str):
+        if mode not in FITS:
+            raise ValueError(f"fit {mode!r}: expected 'stretch', 'contain' or 'cover'")
+        mode = FITS[mode]
+    s, so, do = (ctypes.c_int32 * 4)(*[int(v) for v in src]), (ctypes.c_int32 * 4)(), (ctypes.c_int32 * 4)()
+    check(lib().mp2vg_tensor_fit(int(mode), s, int(par[0]), int(par[1]), int(size[0]), int(size[1]), so, do),
+          "tensor_fit")
+    return tuple(so), tuple(do)
+
+
+def placement(size, crop, coded, place=None, fit=None, pixel_aspect=(1, 1), pad=(0, 0, 0)):
+    """(crop, Place or None) of an export's place / fit / pixel_aspect / pad arguments: `place` is
+    the picture's rectangle in the output; `fit` computes it (and, for "cover", the crop) from the
+    shape crop (None: the coded frame, coded = (w, h)) is shown at with pixels of pixel_aspect.
+    Neither: (crop, None), the export without a placement."""
+    if place is not None and fit is not None:
+        raise ValueError("place and fit exclude each other")
+    if fit is not None:
+        src = (0, 0, int(coded[0]), int(coded[1])) if crop is None else tuple(int(v) for v in crop)
+        crop, place = tensor_fit(fit, src, pixel_aspect, size)
+    return crop, None if place is None else make_place(place, pad)
 
 
 def field_mode(field):

@@ -1943,11 +1943,16 @@ extern "C" int mp2vg_tensor_weights(int32_t src, int32_t out, int32_t* first, in
 }
 
 namespace mp2vg {
-int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int32_t rect[4], int32_t* elem) {
+// place = null or a rectangle of four zeros: no placement, dst[] = the whole output.  With a
+// placement the ratio rule is the rectangle's, not the output's.
+int check_tensor_placed(const mp2vg_tensor_t* t, const mp2vg_tensor_place_t* place, int32_t coded_w, int32_t coded_h,
+                        int32_t rect[4], int32_t* elem, int32_t dst[4], bool* placed) {
     int32_t k[5];
     if (!t) return MP2VG_E_INVALID;
     const bool whole = !t->src_w && !t->src_h;
     const int64_t sw = whole ? coded_w : t->src_w, sh = whole ? coded_h : t->src_h;
+    const bool on = place && (place->dst_x || place->dst_y || place->dst_w || place->dst_h);
+    const int64_t dw = on ? place->dst_w : t->out_w, dh = on ? place->dst_h : t->out_h;
     const char* why = nullptr;
     if (t->layout != MP2VG_EXPORT_RGB_PLANAR && t->layout != MP2VG_EXPORT_RGB_PACKED) why = "layout";
     else if (t->chroma != MP2VG_EXPORT_CHROMA_NEAREST && t->chroma != MP2VG_EXPORT_CHROMA_LINEAR) why = "chroma mode";
@@ -1958,7 +1963,12 @@ int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int3
              t->src_x + sw > coded_w || t->src_y + sh > coded_h)
         why = "source rectangle";
     else if (t->out_w < 1 || t->out_h < 1 || t->out_w > kTensorMaxOut || t->out_h > kTensorMaxOut) why = "output size";
-    else if (sw > 32 * (int64_t)t->out_w || sh > 32 * (int64_t)t->out_h) why = "ratio (above 32)";
+    else if (place && (place->reserved0 || place->reserved[0] || place->reserved[1] || place->reserved[2]))
+        why = "placement (reserved fields)";
+    else if (on && (place->dst_x < 0 || place->dst_y < 0 || dw < 1 || dh < 1 ||
+                    (int64_t)place->dst_x + dw > t->out_w || (int64_t)place->dst_y + dh > t->out_h))
+        why = "placement (rectangle outside the output)";
+    else if (sw > 32 * dw || sh > 32 * dh) why = "ratio (above 32)";
     else
         for (int c = 0; c < 3 && !why; c++) {
             if (!std::isfinite(t->scale[c]) || !std::isfinite(t->bias[c])) why = "scale / bias (not finite)";
@@ -1971,7 +1981,16 @@ int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int3
     }
     rect[0] = t->src_x, rect[1] = t->src_y, rect[2] = (int32_t)sw, rect[3] = (int32_t)sh;
     *elem = t->dtype == MP2VG_TENSOR_U8 ? 1 : t->dtype == MP2VG_TENSOR_F32 ? 4 : 2;
+    dst[0] = on ? place->dst_x : 0, dst[1] = on ? place->dst_y : 0, dst[2] = (int32_t)dw, dst[3] = (int32_t)dh;
+    // a rectangle that is the whole output has nothing to pad: the launch without placement
+    *placed = on && (dst[0] || dst[1] || dst[2] != t->out_w || dst[3] != t->out_h);
     return MP2VG_OK;
+}
+
+int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int32_t rect[4], int32_t* elem) {
+    int32_t dst[4];
+    bool placed;
+    return check_tensor_placed(t, nullptr, coded_w, coded_h, rect, elem, dst, &placed);
 }
 
 int tensor_tables(const int32_t rect[4], int32_t out_w, int32_t out_h, size_t lead, TensorTables* tt) {
@@ -2016,6 +2035,77 @@ extern "C" int mp2vg_tensor_bytes(const mp2vg_config_t* cfg, const mp2vg_tensor_
     int32_t rect[4], elem;
     if (int rc = check_tensor(t, cfg->width, cfg->height, rect, &elem)) return rc;
     *bytes = (uint64_t)n * 3 * (uint64_t)t->out_w * (uint64_t)t->out_h * (uint64_t)elem;
+    return MP2VG_OK;
+}
+
+// ---- placement helpers (include/mp2vg.h: mp2vg_tensor_fit, mp2vg_stream_pixel_aspect); host only ----
+
+static_assert(sizeof(mp2vg_tensor_place_t) == 32 && sizeof(mp2vg_tensor_t) == 80, "ABI: struct sizes");
+static int64_t rnd_div(int64_t p, int64_t q) { return (2 * p + q) / (2 * q); }
+static int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+extern "C" int mp2vg_tensor_fit(int32_t mode, const int32_t src[4], int32_t par_n, int32_t par_d, int32_t out_w,
+                                int32_t out_h, int32_t src_out[4], int32_t dst_out[4]) {
+    if (!src || !src_out || !dst_out) return MP2VG_E_INVALID;
+    const int64_t x = src[0], y = src[1], w = src[2], h = src[3], ow = out_w, oh = out_h;
+    const char* why = nullptr;
+    if (mode < MP2VG_FIT_STRETCH || mode > MP2VG_FIT_COVER) why = "mode outside MP2VG_FIT_*";
+    else if (x < 0 || y < 0 || w < 1 || h < 1 || w > kTensorMaxOut || h > kTensorMaxOut) why = "source rectangle";
+    else if (ow < 1 || oh < 1 || ow > kTensorMaxOut || oh > kTensorMaxOut) why = "output size";
+    else if (par_n < 1 || par_d < 1 || par_n > (1 << 24) || par_d > (1 << 24)) why = "pixel aspect";
+    if (why) {
+        set_error(std::string("tensor fit: bad ") + why);
+        return MP2VG_E_INVALID;
+    }
+    int64_t s[4] = {x, y, w, h}, d[4] = {0, 0, ow, oh};
+    const int64_t A = w * par_n, B = h * par_d;  // the displayed shape A : B, below 2^38 each
+    const bool wide = A * oh >= B * ow;          // at least as wide as the output (below 2^52)
+    if (mode == MP2VG_FIT_CONTAIN) {
+        if (wide) d[3] = clamp64(rnd_div(B * ow, A), 1, oh);
+        else d[2] = clamp64(rnd_div(A * oh, B), 1, ow);
+        d[0] = (ow - d[2]) >> 1, d[1] = (oh - d[3]) >> 1;
+    } else if (mode == MP2VG_FIT_COVER) {
+        if (wide) {
+            s[2] = clamp64(rnd_div(h * par_d * ow, (int64_t)par_n * oh), 1, w);
+            s[0] = x + ((w - s[2]) >> 1);
+        } else {
+            s[3] = clamp64(rnd_div(w * par_n * oh, (int64_t)par_d * ow), 1, h);
+            s[1] = y + ((h - s[3]) >> 1);
+        }
+    }
+    if (s[2] > 32 * d[2] || s[3] > 32 * d[3]) {
+        set_error("tensor fit: the result's ratio is above 32");
+        return MP2VG_E_INVALID;
+    }
+    for (int i = 0; i < 4; i++) src_out[i] = (int32_t)s[i], dst_out[i] = (int32_t)d[i];
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_stream_pixel_aspect(const mp2vg_stream_headers_t* h, int32_t* par_n, int32_t* par_d) {
+    if (!h || !par_n || !par_d) return MP2VG_E_INVALID;
+    const uint32_t code = h->sequence_header.aspect_ratio_information;
+    if (code < 1 || code > 4) {
+        set_error("aspect_ratio_information " + std::to_string(code) + " gives no pixel aspect");
+        return MP2VG_E_UNSUPPORTED;
+    }
+    *par_n = *par_d = 1;
+    if (code == 1) return MP2VG_OK;
+    const mp2vg_sequence_display_extension_t& de = h->sequence_display_extension;
+    int64_t W = h->sequence_header.horizontal_size_value | (int64_t)h->sequence_extension.horizontal_size_extension << 12;
+    int64_t H = h->sequence_header.vertical_size_value | (int64_t)h->sequence_extension.vertical_size_extension << 12;
+    if (h->have_sequence_display_extension && de.display_horizontal_size && de.display_vertical_size)
+        W = de.display_horizontal_size, H = de.display_vertical_size;
+    if (W < 1 || H < 1) {
+        set_error("pixel aspect: the stream's size is 0");
+        return MP2VG_E_INVALID;
+    }
+    const int64_t dw = code == 2 ? 4 : code == 3 ? 16 : 221, dh = code == 2 ? 3 : code == 3 ? 9 : 100;
+    int64_t n = dw * H, d = dh * W, a = n, b = d;
+    while (b) {
+        const int64_t r = a % b;
+        a = b, b = r;
+    }
+    *par_n = (int32_t)(n / a), *par_d = (int32_t)(d / a);
     return MP2VG_OK;
 }
 

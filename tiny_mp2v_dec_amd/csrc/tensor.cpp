@@ -1,6 +1,7 @@
 // tensor.cpp — host entry points of the tensor export that enqueue the kernel (tensor.hip):
-// mp2vg_tensor_slots_fields and mp2vg_tensor_planes_field, and mp2vg_tensor_slots and
-// mp2vg_tensor_planes, their all-PROGRESSIVE cases.  The host-only part (tap tables, validation, sizes)
+// mp2vg_tensor_slots_placed and mp2vg_tensor_planes_placed, and their cases without a placement
+// (mp2vg_tensor_slots_fields, mp2vg_tensor_planes_field) and all PROGRESSIVE (mp2vg_tensor_slots,
+// mp2vg_tensor_planes).  The host-only part (tap tables, validation, sizes)
 // lives in runtime.cpp; the context's side (slot table, staging ring, events) is the RGB export's.
 #include <hip/hip_runtime.h>
 
@@ -17,8 +18,9 @@ using namespace mp2vg;
 static constexpr int32_t kTensorMaxFrames = 65535;  // the frame index is a grid dimension
 
 // coefficients, rectangle, normalisation and the tables at d (the device copy of tt.blob)
+// and the placement: the picture's rectangle pd in the output, the pad colour in units of Q
 static void tensor_args(TensorArgs* a, const mp2vg_tensor_t* t, const int32_t rect[4], const TensorTables& tt,
-                        const int32_t* d, void* dst) {
+                        const int32_t* d, void* dst, const int32_t pd[4], const mp2vg_tensor_place_t* place) {
     int32_t k[5];
     mp2vg_export_coefficients(t->matrix, k);
     a->cy = k[0], a->crv = k[1], a->cgu = k[2], a->cgv = k[3], a->cbu = k[4];
@@ -33,6 +35,8 @@ static void tensor_args(TensorArgs* a, const mp2vg_tensor_t* t, const int32_t re
     a->hmax = tt.hmax, a->vmax = tt.vmax;
     for (int c = 0; c < 3; c++) a->scale[c] = t->scale[c], a->bias[c] = t->bias[c];
     a->dst = dst;
+    a->dst_x = pd[0], a->dst_y = pd[1], a->dst_w = pd[2], a->dst_h = pd[3];
+    for (int c = 0; c < 3; c++) a->padq[c] = place ? 64 * (int32_t)place->pad[c] : 0;
 }
 
 static int check_dst(const mp2vg_tensor_t* t, int32_t n, int32_t elem, const void* dst, uint64_t dst_bytes) {
@@ -60,8 +64,9 @@ static int check_field(int32_t field, int32_t cf, int32_t coded_h) {
     return MP2VG_OK;
 }
 
-extern "C" int mp2vg_tensor_slots_fields(mp2vg_ctx_t* c, const int32_t* slots, const int32_t* fields, int32_t n,
-                                         const mp2vg_tensor_t* t, void* dst, uint64_t dst_bytes) {
+extern "C" int mp2vg_tensor_slots_placed(mp2vg_ctx_t* c, const int32_t* slots, const int32_t* fields, int32_t n,
+                                         const mp2vg_tensor_t* t, const mp2vg_tensor_place_t* place, void* dst,
+                                         uint64_t dst_bytes) {
     if (!c || !slots || !t || !dst || n <= 0 || n > kTensorMaxFrames) return MP2VG_E_INVALID;
     ExportSource s;
     export_source(c, &s);
@@ -76,12 +81,13 @@ extern "C" int mp2vg_tensor_slots_fields(mp2vg_ctx_t* c, const int32_t* slots, c
         if (int rc = check_field(fields[i], s.cf, s.ph)) return rc;
         field_modes |= fields[i] != MP2VG_FIELD_PROGRESSIVE;
     }
-    int32_t rect[4], elem;
-    if (int rc = check_tensor(t, s.pw, s.ph, rect, &elem)) return rc;
+    int32_t rect[4], elem, pd[4];
+    bool placed;
+    if (int rc = check_tensor_placed(t, place, s.pw, s.ph, rect, &elem, pd, &placed)) return rc;
     if (int rc = check_dst(t, n, elem, dst, dst_bytes)) return rc;
-    // staged in front of the tables: the slot list, then the field list
+    // staged in front of the tables (those of the picture's rectangle): the slot list, then the field list
     TensorTables tt;
-    if (int rc = tensor_tables(rect, t->out_w, t->out_h, (size_t)n * (field_modes ? 2 : 1), &tt)) return rc;
+    if (int rc = tensor_tables(rect, pd[2], pd[3], (size_t)n * (field_modes ? 2 : 1), &tt)) return rc;
     memcpy(tt.blob.data(), slots, sizeof(int32_t) * n);
     if (field_modes) memcpy(tt.blob.data() + n, fields, sizeof(int32_t) * n);
     HIPCHK(hipSetDevice(s.device));
@@ -99,12 +105,18 @@ extern "C" int mp2vg_tensor_slots_fields(mp2vg_ctx_t* c, const int32_t* slots, c
     }
     a.cw = s.cw;
     a.ch = s.ch;
-    tensor_args(&a, t, rect, tt, d, dst);
+    tensor_args(&a, t, rect, tt, d, dst, pd, place);
     // the list's copy is in flight: its events are recorded whether or not the launch succeeded
-    const hipError_t le = launch_tensor(s.cf, t->layout, t->chroma, t->dtype, field_modes, a, tt.nsegs, n, s.stream);
+    const hipError_t le =
+        launch_tensor(s.cf, t->layout, t->chroma, t->dtype, field_modes, placed, a, tt.nsegs, n, s.stream);
     const int rc = export_enqueued(c);
     HIPCHK(le);
     return rc;
+}
+
+extern "C" int mp2vg_tensor_slots_fields(mp2vg_ctx_t* c, const int32_t* slots, const int32_t* fields, int32_t n,
+                                         const mp2vg_tensor_t* t, void* dst, uint64_t dst_bytes) {
+    return mp2vg_tensor_slots_placed(c, slots, fields, n, t, nullptr, dst, dst_bytes);
 }
 
 extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t n, const mp2vg_tensor_t* t, void* dst,
@@ -112,9 +124,10 @@ extern "C" int mp2vg_tensor_slots(mp2vg_ctx_t* c, const int32_t* slots, int32_t 
     return mp2vg_tensor_slots_fields(c, slots, nullptr, n, t, dst, dst_bytes);
 }
 
-extern "C" int mp2vg_tensor_planes_field(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
-                                         int32_t cf, int32_t coded_w, int32_t coded_h, int32_t field,
-                                         const mp2vg_tensor_t* t, void* dst, uint64_t dst_bytes) {
+extern "C" int mp2vg_tensor_planes_placed(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                                          int32_t cf, int32_t coded_w, int32_t coded_h, int32_t field,
+                                          const mp2vg_tensor_t* t, const mp2vg_tensor_place_t* place, void* dst,
+                                          uint64_t dst_bytes) {
     if (!planes || !stride || !t || !dst || device < 0 || cf < 1 || cf > 3 || coded_w <= 0 || coded_h <= 0)
         return MP2VG_E_INVALID;
     if (int rc = check_field(field, cf, coded_h)) return rc;
@@ -129,11 +142,12 @@ extern "C" int mp2vg_tensor_planes_field(int32_t device, const uint8_t* const pl
             set_error("tensor: planes must be 4-byte aligned, strides multiples of 4 and at least the plane width");
             return MP2VG_E_INVALID;
         }
-    int32_t rect[4], elem;
-    if (int rc = check_tensor(t, coded_w, coded_h, rect, &elem)) return rc;
+    int32_t rect[4], elem, pd[4];
+    bool placed;
+    if (int rc = check_tensor_placed(t, place, coded_w, coded_h, rect, &elem, pd, &placed)) return rc;
     if (int rc = check_dst(t, 1, elem, dst, dst_bytes)) return rc;
     TensorTables tt;
-    if (int rc = tensor_tables(rect, t->out_w, t->out_h, 0, &tt)) return rc;
+    if (int rc = tensor_tables(rect, pd[2], pd[3], 0, &tt)) return rc;
     HIPCHK(hipSetDevice(device));
     int32_t* d = nullptr;
     const size_t bytes = tt.blob.size() * sizeof(int32_t);
@@ -150,14 +164,20 @@ extern "C" int mp2vg_tensor_planes_field(int32_t device, const uint8_t* const pl
         a.ch = ch;
         a.field = field;
         a.coded_h = coded_h;
-        tensor_args(&a, t, rect, tt, d, dst);
-        e = launch_tensor(cf, t->layout, t->chroma, t->dtype, field != MP2VG_FIELD_PROGRESSIVE, a, tt.nsegs, 1,
+        tensor_args(&a, t, rect, tt, d, dst, pd, place);
+        e = launch_tensor(cf, t->layout, t->chroma, t->dtype, field != MP2VG_FIELD_PROGRESSIVE, placed, a, tt.nsegs, 1,
                           nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     hipFree(d);
     HIPCHK(e);
     return MP2VG_OK;
+}
+
+extern "C" int mp2vg_tensor_planes_field(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                                         int32_t cf, int32_t coded_w, int32_t coded_h, int32_t field,
+                                         const mp2vg_tensor_t* t, void* dst, uint64_t dst_bytes) {
+    return mp2vg_tensor_planes_placed(device, planes, stride, cf, coded_w, coded_h, field, t, nullptr, dst, dst_bytes);
 }
 
 extern "C" int mp2vg_tensor_planes(int32_t device, const uint8_t* const planes[3], const int32_t stride[3], int32_t cf,

@@ -31,9 +31,16 @@
 // chroma siting per line, and for TOP / BOTTOM a walk over the field's lines alone, with the rows
 // between them made from the rounded average of two converted lines (comment at the walk).
 //
+// Placement (mp2vg_tensor_slots_placed, include/mp2vg.h "Placement"): a third instantiation,
+// PLACED = true, always with the field row walk (a placed launch of PROGRESSIVE frames runs that walk
+// in mode PROGRESSIVE), so the two above keep their code.  blockIdx.y runs over row pairs of the
+// canvas; whether a canvas row is a picture row is uniform, the vertical pass accumulates for the
+// picture rows of the pair only (none: skipped), and the horizontal pass writes the pad through the
+// same normalise / cast as the picture (comments at both).
+//
 // Static resources (hipcc -O3, --offload-arch=gfx950, 40 variants each): 60-68 VGPRs without
-// field modes, 65-72 with, no scratch, 24576 B LDS per workgroup, which sets 6 waves per SIMD
-// (up to 80 VGPRs keep that; measured speed, also of the one-row split this replaced:
+// field modes, 65-72 with, 65-74 placed, no scratch, 24576 B LDS per workgroup, which sets 6 waves
+// per SIMD (up to 80 VGPRs keep that; measured speed, also of the one-row split this replaced:
 // profiles/export/tensor.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -113,9 +120,12 @@ __device__ __forceinline__ uint16_t bf16_rne(float f) {
 }
 
 // FIELDS = false: every frame PROGRESSIVE (mp2vg_tensor_slots / mp2vg_tensor_planes); true: the
-// frame's MP2VG_FIELD_* mode picks the row walk of the vertical pass
-template <int CF, bool LINEAR, bool PACKED, int DTYPE, bool FIELDS>
+// frame's MP2VG_FIELD_* mode picks the row walk of the vertical pass.
+// PLACED = true (with FIELDS = true only): out_w x out_h is a canvas, the tables are those of the
+// picture's rectangle dst_w x dst_h in it and everything outside the rectangle is the pad colour.
+template <int CF, bool LINEAR, bool PACKED, int DTYPE, bool FIELDS, bool PLACED>
 __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
+    static_assert(FIELDS || !PLACED, "the placed kernel rides the field row walk");
     __shared__ alignas(8) int16_t lds[2][3][kTensorSegCols];
     const int tid = (int)threadIdx.x;
     const int oy = 2 * (int)blockIdx.y;         // output rows oy and, unless oy is the last, oy + 1
@@ -129,11 +139,30 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
 
     // vertical pass over the union of the two rows' source rows (vfirst and the range ends never
     // decrease with the output row); a row outside one output row's taps has weight 0 there
-    const int f0 = a.vfirst[oy], c0 = a.vcount[oy];
-    const int f1 = two ? a.vfirst[oy + 1] : f0, c1 = two ? a.vcount[oy + 1] : 0;
-    const int nrows = max(f0 + c0, f1 + c1) - f0;
-    const int32_t* qv0 = a.vw + (size_t)oy * a.vmax;
-    const int32_t* qv1 = qv0 + (two ? a.vmax : 0);
+    int f0, c0, f1, c1, nrows;
+    const int32_t *qv0, *qv1;
+    // placement (uniform over the workgroup): canvas row oy + t is a picture row (pic0 / pic1) when it
+    // lies in the rectangle; its table row is then oy + t - dst_y.  A pair can be pad + picture or
+    // picture + pad: the pad row has no taps (count 0, its first row the picture row's, so the
+    // union is the picture row's range) and reads the weights of a row that exists.
+    bool pic0 = true, pic1 = two;
+    if (!PLACED) {
+        f0 = a.vfirst[oy], c0 = a.vcount[oy];
+        f1 = two ? a.vfirst[oy + 1] : f0, c1 = two ? a.vcount[oy + 1] : 0;
+        nrows = max(f0 + c0, f1 + c1) - f0;
+        qv0 = a.vw + (size_t)oy * a.vmax;
+        qv1 = qv0 + (two ? a.vmax : 0);
+    } else {
+        const int r0 = oy - a.dst_y;
+        pic0 = r0 >= 0 && r0 < a.dst_h;
+        pic1 = two && r0 + 1 >= 0 && r0 + 1 < a.dst_h;
+        const int ra = pic0 ? r0 : pic1 ? r0 + 1 : 0, rb = pic1 ? r0 + 1 : ra;  // rows inside the tables
+        f0 = a.vfirst[ra], c0 = pic0 ? a.vcount[ra] : 0;
+        f1 = pic1 ? a.vfirst[rb] : f0, c1 = pic1 ? a.vcount[rb] : 0;
+        nrows = max(f0 + c0, f1 + c1) - f0;
+        qv0 = a.vw + (size_t)ra * a.vmax;
+        qv1 = a.vw + (size_t)rb * a.vmax;
+    }
     // field modes (uniform over the workgroup).  WEAVE and PROGRESSIVE walk every row of the union
     // as above, with the line's own chroma siting.  TOP / BOTTOM (parity par) walk only the field's
     // lines z = z0, z0 + 2 .. z1: from the line above the first tap row when that row is an
@@ -162,7 +191,8 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
         const int q = qv1[min(max(k + f0 - f1, 0), a.vmax - 1)];
         return k + f0 - f1 >= 0 && k + f0 - f1 < c1 ? q : 0;
     };
-    for (int u = tid; u < nunits; u += 256) {
+    // (a workgroup whose rows are both pad has no vertical pass; the barrier below stays uniform)
+    for (int u = tid; u < (!PLACED || pic0 || pic1 ? nunits : 0); u += 256) {
         const int x0 = a.src_x + base + 4 * u;
         int aR[2][4] = {}, aG[2][4] = {}, aB[2][4] = {};
         if (!FIELDS) {
@@ -237,27 +267,60 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     // horizontal pass: one output element (row, pixel, channel) per lane
     const int nout = o_end - o_begin;
     const size_t w = (size_t)a.out_w, h = (size_t)a.out_h;
-    for (int idx = tid; idx < (two ? 6 : 3) * nout; idx += 256) {
-        const int t = idx >= 3 * nout ? 1 : 0, e = idx - 3 * nout * t;
-        int c, o;
-        if (PACKED) {
-            o = e / 3;
-            c = e - 3 * o;
+    // Placement: the canvas columns [xb, xe) of row oy + t this workgroup writes.  In a picture row
+    // a segment writes its own picture columns, the first segment also the pad on their left and
+    // the last one the pad on their right; a pad row is written whole by the first segment's
+    // workgroup.  So every element of the canvas has exactly one writer.
+    const int px0 = PLACED ? a.dst_x + o_begin : 0, px1 = PLACED ? a.dst_x + o_end : 0;
+    int xb0 = 0, xb1 = 0, n0 = nout, n1 = two ? nout : 0;
+    if (PLACED) {
+        const bool first = blockIdx.x == 0, last = blockIdx.x + 1 == gridDim.x;
+        const int xe = last ? a.out_w : px1;  // where a picture row of this workgroup ends
+        xb0 = pic0 && !first ? px0 : 0;
+        xb1 = pic1 && !first ? px0 : 0;
+        n0 = pic0 ? xe - xb0 : first ? a.out_w : 0;
+        n1 = pic1 ? xe - xb1 : first && two ? a.out_w : 0;
+    }
+    for (int idx = tid; idx < (PLACED ? 3 * (n0 + n1) : (two ? 6 : 3) * nout); idx += 256) {
+        int t, c, o, Q;
+        if (!PLACED) {
+            t = idx >= 3 * nout ? 1 : 0;
+            const int e = idx - 3 * nout * t;
+            if (PACKED) {
+                o = e / 3;
+                c = e - 3 * o;
+            } else {
+                c = e >= 2 * nout ? 2 : e >= nout ? 1 : 0;
+                o = e - c * nout;
+            }
+            o += o_begin;
         } else {
-            c = e >= 2 * nout ? 2 : e >= nout ? 1 : 0;
-            o = e - c * nout;
+            t = idx >= 3 * n0 ? 1 : 0;
+            const int e = idx - (t ? 3 * n0 : 0), nt = t ? n1 : n0;
+            if (PACKED) {
+                o = e / 3;
+                c = e - 3 * o;
+            } else {
+                c = e >= 2 * nt ? 2 : e >= nt ? 1 : 0;
+                o = e - c * nt;
+            }
+            o += t ? xb1 : xb0;  // the canvas column
         }
-        o += o_begin;
-        // every lane runs the axis' longest tap count, so the loads of several taps are in flight:
-        // the table's rows are zero from the column's tap count on, and a V index past the window is clamped (its
-        // weight is zero, whatever the LDS holds there)
-        const int16_t* v = &lds[t][c][0];
-        const int v0 = a.hfirst[o] - base;
-        const int32_t* qh = a.hw + (size_t)o * a.hmax;
-        int sum = 8192;
+        if (!PLACED || ((t ? pic1 : pic0) && o >= px0 && o < px1)) {
+            const int op = PLACED ? o - a.dst_x : o;  // the column of the tables
+            // every lane runs the axis' longest tap count, so the loads of several taps are in flight:
+            // the table's rows are zero from the column's tap count on, and a V index past the window is clamped (its
+            // weight is zero, whatever the LDS holds there)
+            const int16_t* v = &lds[t][c][0];
+            const int v0 = a.hfirst[op] - base;
+            const int32_t* qh = a.hw + (size_t)op * a.hmax;
+            int sum = 8192;
 #pragma unroll 4
-        for (int k = 0; k < a.hmax; k++) sum += __mul24(qh[k], (int)v[min(v0 + k, kTensorSegCols - 1)]);
-        const int Q = sum >> 14;
+            for (int k = 0; k < a.hmax; k++) sum += __mul24(qh[k], (int)v[min(v0 + k, kTensorSegCols - 1)]);
+            Q = sum >> 14;
+        } else {
+            Q = c == 0 ? a.padq[0] : c == 1 ? a.padq[1] : a.padq[2];  // through the same normalise and cast below
+        }
         const size_t y = (size_t)(oy + t);
         const size_t at = PACKED ? ((f * h + y) * w + (size_t)o) * 3 + (size_t)c
                                  : ((f * 3 + (size_t)c) * h + y) * w + (size_t)o;
@@ -277,47 +340,60 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     }
 }
 
-template <int CF, bool LINEAR, bool PACKED, bool FIELDS>
+template <int CF, bool LINEAR, bool PACKED, bool FIELDS, bool PLACED>
 static void launch_dtype(int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
     const dim3 block(256, 1, 1);
     if (dtype == MP2VG_TENSOR_U8)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8, FIELDS>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8, FIELDS, PLACED>), grid, block, 0, stream,
+                           a);
     else if (dtype == MP2VG_TENSOR_F16)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16, FIELDS>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16, FIELDS, PLACED>), grid, block, 0, stream,
+                           a);
     else if (dtype == MP2VG_TENSOR_BF16)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16, FIELDS>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16, FIELDS, PLACED>), grid, block, 0,
+                           stream, a);
     else
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32, FIELDS>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32, FIELDS, PLACED>), grid, block, 0, stream,
+                           a);
 }
 
-template <int CF, bool FIELDS>
+template <int CF, bool FIELDS, bool PLACED>
 static void launch_cf(int layout, int chroma, int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
     const bool lin = chroma == MP2VG_EXPORT_CHROMA_LINEAR && CF != 3;  // 4:4:4: LINEAR is NEAREST
     if (layout == MP2VG_EXPORT_RGB_PACKED) {
         if (lin)
-            launch_dtype<CF, CF != 3, true, FIELDS>(dtype, a, grid, stream);
+            launch_dtype<CF, CF != 3, true, FIELDS, PLACED>(dtype, a, grid, stream);
         else
-            launch_dtype<CF, false, true, FIELDS>(dtype, a, grid, stream);
+            launch_dtype<CF, false, true, FIELDS, PLACED>(dtype, a, grid, stream);
     } else {
         if (lin)
-            launch_dtype<CF, CF != 3, false, FIELDS>(dtype, a, grid, stream);
+            launch_dtype<CF, CF != 3, false, FIELDS, PLACED>(dtype, a, grid, stream);
         else
-            launch_dtype<CF, false, false, FIELDS>(dtype, a, grid, stream);
+            launch_dtype<CF, false, false, FIELDS, PLACED>(dtype, a, grid, stream);
     }
 }
 
-hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, const TensorArgs& a, int nsegs,
-                         int n, hipStream_t stream) {
+// the three walks: without field modes, with them, and placed (which always has them)
+template <int CF>
+static void launch_walk(int layout, int chroma, int dtype, bool field_modes, bool placed, const TensorArgs& a, dim3 grid,
+                        hipStream_t stream) {
+    if (placed)
+        launch_cf<CF, true, true>(layout, chroma, dtype, a, grid, stream);
+    else if (field_modes)
+        launch_cf<CF, true, false>(layout, chroma, dtype, a, grid, stream);
+    else
+        launch_cf<CF, false, false>(layout, chroma, dtype, a, grid, stream);
+}
+
+hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, bool placed, const TensorArgs& a,
+                         int nsegs, int n, hipStream_t stream) {
     const dim3 grid((unsigned)nsegs, (unsigned)((a.out_h + 1) / 2), (unsigned)n);
     if (cf == 1)
-        field_modes ? launch_cf<1, true>(layout, chroma, dtype, a, grid, stream)
-                    : launch_cf<1, false>(layout, chroma, dtype, a, grid, stream);
+        launch_walk<1>(layout, chroma, dtype, field_modes, placed, a, grid, stream);
     else if (cf == 2)
-        field_modes ? launch_cf<2, true>(layout, chroma, dtype, a, grid, stream)
-                    : launch_cf<2, false>(layout, chroma, dtype, a, grid, stream);
+        launch_walk<2>(layout, chroma, dtype, field_modes, placed, a, grid, stream);
     else
-        field_modes ? launch_cf<3, true>(layout, chroma, dtype, a, grid, stream)
-                    : launch_cf<3, false>(layout, chroma, dtype, a, grid, stream);
+        launch_walk<3>(layout, chroma, dtype, field_modes, placed, a, grid, stream);
     return hipGetLastError();
 }
 

@@ -42,16 +42,25 @@ struct TensorArgs {
     const int32_t* fields;
     int32_t field;
     int32_t coded_h;
+    // placement, behind those (read by the placed kernel only): the picture's rectangle in the
+    // out_w x out_h canvas; the tables are then those of dst_w x dst_h.  padq[c] = 64 pad[c].
+    int32_t dst_x, dst_y, dst_w, dst_h;
+    int32_t padq[3];
 };
 
-// cf 1..3; layout, chroma, dtype of the mp2vg_tensor_t; grid = (nsegs, row pairs, n).
+// cf 1..3; layout, chroma, dtype of the mp2vg_tensor_t; grid = (nsegs, row pairs of out_h, n).
 // field_modes = false: every frame PROGRESSIVE, the kernel without the field row walk.
-hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, const TensorArgs& a, int nsegs,
-                         int n, hipStream_t stream);
+// placed = true: the placed kernel (always with the field row walk, whatever field_modes says).
+hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, bool placed, const TensorArgs& a,
+                         int nsegs, int n, hipStream_t stream);
 
 // host-only side (runtime.cpp)
 // checks t against a coded size; the source rectangle in rect[4] (x, y, w, h) and the element size
 int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int32_t rect[4], int32_t* elem);
+// the same with a placement (null: none): dst[4] = the picture's rectangle in the output (the whole
+// output without a placement), *placed = whether anything is left to pad
+int check_tensor_placed(const mp2vg_tensor_t* t, const mp2vg_tensor_place_t* place, int32_t coded_w, int32_t coded_h,
+                        int32_t rect[4], int32_t* elem, int32_t dst[4], bool* placed);
 // The int32 tables of a validated tensor export, behind `lead` entries left for the caller (the
 // slot list, then the field list of a launch with field modes): segs, hfirst, hw, vfirst, vcount,
 // vw.  off[6] = the index of each in blob.

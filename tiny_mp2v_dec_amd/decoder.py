@@ -113,21 +113,31 @@ class frame_c:  # noqa: N801  (reference name)
         return t
 
     def export_tensor(self, size, crop=None, dtype="float16", mean=None, std=None, layout="nchw", chroma="linear",
-                      matrix=1, out=None, field="progressive"):
+                      matrix=1, out=None, field="progressive", place=None, fit=None, pixel_aspect=(1, 1),
+                      pad=(0, 0, 0)):
         """This frame as a cropped, resized, normalised model-input tensor on its device, (1, 3, h,
-        w) or (1, h, w, 3) (mp2vg_tensor_planes_field; arguments as DeviceContext.export_tensor;
-        field = "progressive" / "top" / "bottom" / "weave" or the MP2VG_FIELD_* integer).
+        w) or (1, h, w, 3) (mp2vg_tensor_planes_field, or mp2vg_tensor_planes_placed with place or
+        fit; arguments as DeviceContext.export_tensor; field = "progressive" / "top" / "bottom" /
+        "weave" or the MP2VG_FIELD_* integer).
         Device frames only; complete on return, so the tensor outlives the callback."""
         if not self.is_device:
             raise ValueError("host frame: export_tensor needs a device_frames=True decoder")
         f = self._f
         cf = 3 if f.width[1] == f.width[0] else (2 if f.height[1] == f.height[0] else 1)
+        crop, pl = _lib.placement(size, crop, (f.width[0], f.height[0]), place, fit, pixel_aspect, pad)
         t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
         o = _lib.tensor_out(out, _lib.tensor_shape(t, 1), dtype, f.device)
         planes = (ctypes.c_void_p * 3)(*[self.device_ptr(i) for i in range(3)])
-        check(lib().mp2vg_tensor_planes_field(f.device, planes, f.stride, cf, f.width[0], f.height[0],
-                                              _lib.field_mode(field), ctypes.byref(t), ctypes.c_void_p(o.data_ptr()),
-                                              o.numel() * o.element_size()), "tensor_planes_field")
+        if pl is None:
+            check(lib().mp2vg_tensor_planes_field(f.device, planes, f.stride, cf, f.width[0], f.height[0],
+                                                  _lib.field_mode(field), ctypes.byref(t),
+                                                  ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()),
+                  "tensor_planes_field")
+        else:
+            check(lib().mp2vg_tensor_planes_placed(f.device, planes, f.stride, cf, f.width[0], f.height[0],
+                                                   _lib.field_mode(field), ctypes.byref(t), ctypes.byref(pl),
+                                                   ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()),
+                  "tensor_planes_placed")
         return o
 
     def get_strides(self, i):

@@ -389,7 +389,8 @@ class DeviceContext:
         return t
 
     def export_tensor(self, slots, size, crop=None, dtype="float16", mean=None, std=None, layout="nchw",
-                      chroma="linear", matrix=1, out=None, sync=True, fields=None):
+                      chroma="linear", matrix=1, out=None, sync=True, fields=None, place=None, fit=None,
+                      pixel_aspect=(1, 1), pad=(0, 0, 0)):
         """Frames of `slots` (any order, repeats allowed) as one model-input tensor on this
         context's device (mp2vg_tensor_slots_fields: one fused kernel launch): cropped to crop = (x, y, w,
         h) in luma pixels (None: the coded frame), resized to size = (width, height) with the
@@ -403,19 +404,33 @@ class DeviceContext:
         one of those (or the MP2VG_FIELD_* integers) per slot; a slot listed twice with "top" and
         "bottom" gives both fields of its picture.
 
+        Placement (include/mp2vg.h "Placement", mp2vg_tensor_slots_placed, still one launch): place =
+        (x, y, w, h) puts the resized picture at that rectangle of the size[0] x size[1] output and
+        writes pad = (R, G, B), 8-bit, normalised like a pixel, everywhere else.  fit = "contain"
+        computes the centred rectangle that keeps the shape of the crop shown with pixels of
+        pixel_aspect = (n, d), width : height (records.pixel_aspect gives a stream's); "cover" the
+        centre crop of that shape that fills the output; "stretch" is the export without fit.  place
+        and fit exclude each other; without either the call is the one without a placement.
+
         Stream ordering is export_rgb's: the export runs on the context's own stream behind the
         decodes enqueued so far; work torch has enqueued on `out` must have finished before the
         call, and with sync=False torch must not read the tensor before synchronize().  At most
         65535 slots per call."""
         slots = np.ascontiguousarray(slots, np.int32).ravel()
         modes = _lib.field_modes(fields, len(slots))
+        crop, pl = _lib.placement(size, crop, (self.pw[0], self.ph[0]), place, fit, pixel_aspect, pad)
         t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
         o = _lib.tensor_out(out, _lib.tensor_shape(t, len(slots)), dtype, self.cfg.device)
         i32p = ctypes.POINTER(ctypes.c_int32)
-        check(lib().mp2vg_tensor_slots_fields(self.h, slots.ctypes.data_as(i32p),
-                                              None if modes is None else modes.ctypes.data_as(i32p), len(slots),
-                                              ctypes.byref(t), ctypes.c_void_p(o.data_ptr()),
-                                              o.numel() * o.element_size()), "tensor_slots_fields")
+        fp = None if modes is None else modes.ctypes.data_as(i32p)
+        if pl is None:
+            check(lib().mp2vg_tensor_slots_fields(self.h, slots.ctypes.data_as(i32p), fp, len(slots), ctypes.byref(t),
+                                                  ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()),
+                  "tensor_slots_fields")
+        else:
+            check(lib().mp2vg_tensor_slots_placed(self.h, slots.ctypes.data_as(i32p), fp, len(slots), ctypes.byref(t),
+                                                  ctypes.byref(pl), ctypes.c_void_p(o.data_ptr()),
+                                                  o.numel() * o.element_size()), "tensor_slots_placed")
         if sync:
             self.synchronize()
         return o
@@ -437,6 +452,18 @@ def export_matrix(headers):
     m = ctypes.c_int32()
     check(lib().mp2vg_export_matrix(ctypes.byref(headers), ctypes.byref(m)), "export_matrix")
     return m.value
+
+
+def pixel_aspect(headers):
+    """(n, d), the pixel's width : height of a stream from its aspect_ratio_information
+    (mp2vg_stream_pixel_aspect); Mp2vgError for a code that gives none."""
+    n, d = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().mp2vg_stream_pixel_aspect(ctypes.byref(headers), ctypes.byref(n), ctypes.byref(d)),
+          "stream_pixel_aspect")
+    return n.value, d.value
+
+
+stream_pixel_aspect = pixel_aspect  # for functions with a `pixel_aspect` argument
 
 
 def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0,
@@ -494,7 +521,8 @@ def field_plan(display, flags, fields):
 
 
 def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
-                  layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False, fields=None):
+                  layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False, fields=None, fit=None,
+                  pad=(0, 0, 0), pixel_aspect="stream"):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
     dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
@@ -509,7 +537,13 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     top_field_first, else the bottom one), n frames; "both" 2n frames in temporal order: an
     interlaced picture gives its first field, then its second, a progressive picture its frame
     twice.  repeat_first_field (3:2 pulldown) is reported in Parsed.flags but ignored here: no
-    field is repeated."""
+    field is repeated.
+
+    fit (DeviceContext.export_tensor): "contain" letterboxes the source rectangle (crop, or the
+    rectangle picked above) into size with the pad colour around it, "cover" fills size with its
+    centre crop, both at the shape the stream is shown at: pixel_aspect="stream" takes the stream's
+    own (records.pixel_aspect; a stream whose aspect code gives none raises Mp2vgError, it is not
+    guessed at), a tuple (n, d) overrides it."""
     parsed = (Scan if device_parse else Parsed)(es, width, height, chroma_format)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
@@ -518,6 +552,13 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     if matrix is None:
         matrix = export_matrix(parsed.headers)
     slots, modes = field_plan(parsed.display, parsed.flags, fields)
+    place = None
+    if fit is not None:
+        if isinstance(pixel_aspect, str) and pixel_aspect != "stream":
+            raise ValueError(f"pixel_aspect {pixel_aspect!r}: expected 'stream' or (n, d)")
+        par = stream_pixel_aspect(parsed.headers) if pixel_aspect == "stream" else pixel_aspect
+        pw, ph, _, _ = _lib.geometry(width, height, chroma_format)
+        crop, place = _lib.tensor_fit(fit, (0, 0, pw[0], ph[0]) if crop is None else crop, par, size)
     t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
     out = _lib.tensor_out(None, _lib.tensor_shape(t, len(slots)), dtype, device)
     if not parsed.npics:
@@ -532,7 +573,7 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
             part = slots[i:i + EXPORT_MAX_FRAMES]
             ctx.export_tensor(part, size, crop=crop, dtype=dtype, mean=mean, std=std, layout=layout, chroma=chroma,
                               matrix=matrix, out=out[i:i + len(part)], sync=False,
-                              fields=None if modes is None else modes[i:i + len(part)])
+                              fields=None if modes is None else modes[i:i + len(part)], place=place, pad=pad)
         ctx.synchronize()
         return out
 
