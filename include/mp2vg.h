@@ -417,8 +417,34 @@ int  mp2vg_export_planes(int32_t device, const uint8_t* const planes[3], const i
  * fields 0, and the ratio rule of step 2 holds for the rectangle (src_w <= 32 dst_w, src_h <= 32
  * dst_h; out_w and out_h are then not judged by it), else MP2VG_E_INVALID.  A rectangle of four
  * zeros is the whole output: no placement, pad is never written.  One placement per launch.
+ *
+ * Items (mp2vg_tensor_items / mp2vg_tensor_planes_items): one launch writes n images of one common
+ * out_w x out_h, dtype, layout and normalisation, each from its own source slot, field mode, source
+ * rectangle and mirror flag (mp2vg_tensor_item_t): the random-resized-crop and flip of every sample
+ * of a training batch, or every box of a detector cut from one frame.  Items change where step 1's
+ * rectangle comes from, add a mirror between steps 3 and 4 and generalise step 5; the arithmetic of
+ * every step is untouched.
+ *     Steps 1 to 3: Q_i[out_h][out_w] is the image those steps give for item i's rectangle (src_x,
+ *             src_y, src_w, src_h; all 0 = the whole coded frame) under its field mode: exactly what
+ *             mp2vg_tensor_slots_fields defines for that rectangle and mode.  t->src_* must all be
+ *             0.  The ratio rule of step 2 holds per item and per axis.
+ *     Mirror: with MP2VG_ITEM_HFLIP the element at column x is Q_i[y][out_w - 1 - x]: a pure index
+ *             reversal after both filter passes (not the filter over a mirrored source).
+ *     Step 4 is unchanged.
+ *     Step 5, packed: [n][out_h][out_w][3], unchanged; clip_len is only checked.
+ *     Step 5, planar: with T = clip_len (>= 1, n a multiple of it), b = i / T and k = i % T the
+ *             element is at (((b 3 + c) T + k) out_h + y) out_w + x: [n / T][3][T][out_h][out_w],
+ *             the clip layout of video models.  T = 1 is [n][3][out_h][out_w].
+ *     dst_bytes = n 3 out_w out_h element size, as mp2vg_tensor_bytes gives for any rectangle.
+ * n is 1 .. 65535; flags holds no bit but MP2VG_ITEM_HFLIP and reserved is 0; a field mode other
+ * than PROGRESSIVE has the precondition on the coded height above; else MP2VG_E_INVALID with
+ * nothing written, and mp2vg_last_error names the index of the first offending item.
+ * Tap tables are shared: items of one src_w use one horizontal table (whatever their origin or
+ * height), items of one src_h one vertical table, so the staged bytes grow with the distinct
+ * sizes of a launch, not with n (mp2vg_tensor_items_plan reports them).
  * Out of scope: motion-adaptive deinterlacing, filters other than the triangle, pad modes other
- * than a constant colour, a placement per frame of a launch. */
+ * than a constant colour; for items: a vertical flip, a placement or pad per item (an items launch
+ * has no placement), per-item output sizes and per-item normalisation. */
 enum { MP2VG_TENSOR_U8 = 0, MP2VG_TENSOR_F16 = 1, MP2VG_TENSOR_BF16 = 2, MP2VG_TENSOR_F32 = 3 };
 enum { MP2VG_FIELD_PROGRESSIVE = 0, MP2VG_FIELD_TOP = 1, MP2VG_FIELD_BOTTOM = 2, MP2VG_FIELD_WEAVE = 3 };
 #define MP2VG_TENSOR_MAX_TAPS 65
@@ -506,6 +532,37 @@ int  mp2vg_tensor_planes_placed(int32_t device, const uint8_t* const planes[3], 
 enum { MP2VG_FIT_STRETCH = 0, MP2VG_FIT_CONTAIN = 1, MP2VG_FIT_COVER = 2 };
 int  mp2vg_tensor_fit(int32_t mode, const int32_t src[4], int32_t par_n, int32_t par_d,
                       int32_t out_w, int32_t out_h, int32_t src_out[4], int32_t dst_out[4]);
+
+/* Items (the contract is in the block above the enums). */
+enum { MP2VG_ITEM_HFLIP = 1 };
+typedef struct mp2vg_tensor_item {
+    int32_t slot;                        /* source slot (must be 0 in the planes call) */
+    int32_t field;                       /* MP2VG_FIELD_* */
+    int32_t src_x, src_y, src_w, src_h;  /* luma pixels; all 0 = the whole coded frame */
+    int32_t flags;                       /* MP2VG_ITEM_HFLIP or 0 */
+    int32_t reserved;                    /* must be 0 */
+} mp2vg_tensor_item_t;                   /* 32 bytes */
+/* Image i from items[i] (slots in any order, repeats allowed), all n in one launch.  Ordering,
+ * staging ring, events and limits as mp2vg_tensor_slots; the item records and the shared tap tables
+ * are copied before the call returns.  Every argument is checked before the first HIP call. */
+int  mp2vg_tensor_items(mp2vg_ctx_t* ctx, const mp2vg_tensor_item_t* items, int32_t n,
+                        const mp2vg_tensor_t* t, int32_t clip_len, void* dst_device, uint64_t dst_bytes);
+/* The same kernel over one frame at arbitrary device plane pointers (preconditions of
+ * mp2vg_tensor_planes; every item's slot is 0): many rectangles of one device frame, for example
+ * inside a render callback.  Synchronous, like mp2vg_tensor_planes_placed. */
+int  mp2vg_tensor_planes_items(int32_t device, const uint8_t* const planes[3], const int32_t stride[3],
+                               int32_t chroma_format, int32_t coded_w, int32_t coded_h,
+                               const mp2vg_tensor_item_t* items, int32_t n, const mp2vg_tensor_t* t,
+                               int32_t clip_len, void* dst_device, uint64_t dst_bytes);
+/* Host only, no device: validates t, items, n and clip_len exactly as mp2vg_tensor_items does for a
+ * context of cfg (a slot is checked to be >= 0 only: the slot count belongs to the context) and
+ * reports the launch.  htab[i] / vtab[i] (n entries each, or NULL): the index of item i's
+ * horizontal / vertical tap table, tables numbered in order of first use.  summary = {distinct
+ * horizontal tables, distinct vertical tables, grid.x (the largest segment count of any item), int32
+ * words staged (item records, then the tables)}. */
+int  mp2vg_tensor_items_plan(const mp2vg_config_t* cfg, const mp2vg_tensor_t* t,
+                             const mp2vg_tensor_item_t* items, int32_t n, int32_t clip_len,
+                             int32_t* htab, int32_t* vtab, int32_t summary[4]);
 
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c

@@ -134,6 +134,14 @@ class Place(ctypes.Structure):  # mp2vg_tensor_place_t
 
 
 assert ctypes.sizeof(Place) == 32
+
+
+class Item(ctypes.Structure):  # mp2vg_tensor_item_t
+    _fields_ = [(n, ctypes.c_int32) for n in ("slot", "field", "src_x", "src_y", "src_w", "src_h", "flags", "reserved")]
+
+
+assert ctypes.sizeof(Item) == 32
+ITEM_HFLIP = 1  # MP2VG_ITEM_*
 FIT_STRETCH, FIT_CONTAIN, FIT_COVER = 0, 1, 2  # MP2VG_FIT_*
 FITS = {"stretch": FIT_STRETCH, "contain": FIT_CONTAIN, "cover": FIT_COVER}
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
@@ -163,6 +171,7 @@ EXPORTS = [
     "mp2vg_tensor_weights", "mp2vg_tensor_bytes", "mp2vg_tensor_slots", "mp2vg_tensor_planes",
     "mp2vg_tensor_slots_fields", "mp2vg_tensor_planes_field", "mp2vg_parsed_picture_flags", "mp2vg_scan_picture_flags",
     "mp2vg_tensor_slots_placed", "mp2vg_tensor_planes_placed", "mp2vg_tensor_fit", "mp2vg_stream_pixel_aspect",
+    "mp2vg_tensor_items", "mp2vg_tensor_planes_items", "mp2vg_tensor_items_plan",
     "mp2vg_scan_es", "mp2vg_scan_counts", "mp2vg_scan_pictures", "mp2vg_scan_display_order",
     "mp2vg_scan_gop_index", "mp2vg_scan_shards", "mp2vg_scan_stream_headers", "mp2vg_scan_free",
     "mp2vg_scan_parse_host", "mp2vg_batch_upload_es", "mp2vg_batch_record_counts",
@@ -247,6 +256,10 @@ def lib():
                                        ctypes.c_int),
         "mp2vg_tensor_fit": ([I32, P(I32), I32, I32, I32, I32, P(I32), P(I32)], ctypes.c_int),
         "mp2vg_stream_pixel_aspect": ([P(StreamHeaders), P(I32), P(I32)], ctypes.c_int),
+        "mp2vg_tensor_items": ([VP, P(Item), I32, P(Tensor), I32, VP, U64], ctypes.c_int),
+        "mp2vg_tensor_planes_items": ([I32, P(VP), P(I32), I32, I32, I32, P(Item), I32, P(Tensor), I32, VP, U64],
+                                      ctypes.c_int),
+        "mp2vg_tensor_items_plan": ([P(Config), P(Tensor), P(Item), I32, I32, P(I32), P(I32), P(I32)], ctypes.c_int),
         "mp2vg_parsed_picture_flags": ([VP, P(ctypes.c_uint32), I32], ctypes.c_int),
         "mp2vg_scan_picture_flags": ([VP, P(ctypes.c_uint32), I32], ctypes.c_int),
         "mp2vg_scan_es": ([VP, U64, P(Config), P(VP)], ctypes.c_int),
@@ -413,6 +426,46 @@ def field_modes(fields, n):
     if len(out) != n:
         raise ValueError("fields must hold one mode per slot")
     return out
+
+
+def make_items(slots, crops, flips=None, fields=None, n=None):
+    """(mp2vg_tensor_item_t * n) from the Python spelling.  slots: None (every item slot 0, the
+    planes call), one slot for every item or n slots; crops: None (every item the whole coded frame)
+    or n entries, each (x, y, w, h) in luma pixels or None; flips: None, one bool for every item or
+    n of them (True: MP2VG_ITEM_HFLIP); fields as field_modes.  n defaults to the length of crops,
+    else of slots."""
+    if n is None:
+        n = len(crops) if crops is not None else len(slots)
+    n = int(n)
+
+    def per_item(v, what, scalar):
+        if v is None or isinstance(v, scalar):
+            return [v] * n
+        if len(v) != n:
+            raise ValueError(f"{what} must hold one entry per item ({n})")
+        return list(v)
+
+    slots = per_item(slots, "slots", (int, np.integer))
+    flips = per_item(flips, "flips", (bool, np.bool_))
+    modes = field_modes(fields, n)
+    if crops is not None and len(crops) != n:
+        raise ValueError(f"crops must hold one entry per item ({n})")
+    items = (Item * n)()
+    for i in range(n):
+        x, y, w, h = (0, 0, 0, 0) if crops is None or crops[i] is None else (int(v) for v in crops[i])
+        items[i] = Item(int(slots[i] or 0), 0 if modes is None else int(modes[i]), x, y, w, h,
+                        ITEM_HFLIP if flips[i] else 0, 0)
+    return items
+
+
+def items_shape(t, n, clip_len):
+    """Shape of an items launch: (n, h, w, 3) packed; planar (n, 3, h, w), or (n / T, 3, T, h, w) in
+    clip order for clip_len = T > 1."""
+    if t.layout != EXPORT_RGB_PLANAR or clip_len == 1:
+        return tensor_shape(t, n)
+    if clip_len < 1 or n % clip_len:
+        raise ValueError(f"clip_len {clip_len} must be at least 1 and divide the number of items ({n})")
+    return (n // clip_len, 3, clip_len, t.out_h, t.out_w)
 
 
 def tensor_shape(t, n):

@@ -1995,12 +1995,16 @@ int check_tensor(const mp2vg_tensor_t* t, int32_t coded_w, int32_t coded_h, int3
 
 int tensor_tables(const int32_t rect[4], int32_t out_w, int32_t out_h, size_t lead, TensorTables* tt) {
     std::vector<int32_t> first[2], count[2], w[2];
-    int32_t maxc[2];
+    int32_t maxc[2], cap[2];
     for (int ax = 0; ax < 2; ax++) {
         const int32_t src = rect[2 + ax], out = ax ? out_h : out_w;
-        first[ax].resize(out), count[ax].resize(out), w[ax].resize((size_t)out * MP2VG_TENSOR_MAX_TAPS);
-        if (int rc = mp2vg_tensor_weights(src, out, first[ax].data(), count[ax].data(), w[ax].data(),
-                                          MP2VG_TENSOR_MAX_TAPS))
+        // a row's taps span at most 2 max(src, out) / out + 1 source pixels (mp2vg_tensor_weights: hi - lo =
+        // 4 M over steps of 2 out): rows of that many entries, not of MP2VG_TENSOR_MAX_TAPS, so a launch
+        // of many tables (items) does not spend its time clearing them
+        cap[ax] = (int32_t)std::min<int64_t>(MP2VG_TENSOR_MAX_TAPS,
+                                             2 * (((int64_t)std::max(src, out) + out - 1) / std::max(out, 1)) + 1);
+        first[ax].resize(out), count[ax].resize(out), w[ax].resize((size_t)out * cap[ax]);
+        if (int rc = mp2vg_tensor_weights(src, out, first[ax].data(), count[ax].data(), w[ax].data(), cap[ax]))
             return rc;
         maxc[ax] = *std::max_element(count[ax].begin(), count[ax].end());
     }
@@ -2017,17 +2021,138 @@ int tensor_tables(const int32_t rect[4], int32_t out_w, int32_t out_h, size_t le
     std::vector<int32_t>& b = tt->blob;
     b.assign(lead, 0);
     auto put = [&](int i, const std::vector<int32_t>& v) { tt->off[i] = b.size(), b.insert(b.end(), v.begin(), v.end()); };
-    auto put_w = [&](int i, int ax, int32_t out) {  // rows of MP2VG_TENSOR_MAX_TAPS compacted to the axis' longest
+    auto put_w = [&](int i, int ax, int32_t out) {  // rows of cap[ax] compacted to the axis' longest
         tt->off[i] = b.size();
         for (int32_t o = 0; o < out; o++)
-            b.insert(b.end(), w[ax].begin() + (size_t)o * MP2VG_TENSOR_MAX_TAPS,
-                     w[ax].begin() + (size_t)o * MP2VG_TENSOR_MAX_TAPS + maxc[ax]);
+            b.insert(b.end(), w[ax].begin() + (size_t)o * cap[ax], w[ax].begin() + (size_t)o * cap[ax] + maxc[ax]);
     };
     put(0, segs), put(1, first[0]), put_w(2, 0, out_w);
     put(3, first[1]), put(4, count[1]), put_w(5, 1, out_h);
     return MP2VG_OK;
 }
+
+int check_tensor_field(int32_t field, int32_t cf, int32_t coded_h) {
+    if (field < MP2VG_FIELD_PROGRESSIVE || field > MP2VG_FIELD_WEAVE) {
+        set_error("tensor: field mode outside MP2VG_FIELD_*");
+        return MP2VG_E_INVALID;
+    }
+    if (field != MP2VG_FIELD_PROGRESSIVE && (coded_h & (cf == 1 ? 3 : 1))) {
+        set_error("tensor: a field mode needs an even coded height (4:2:0: a multiple of 4)");
+        return MP2VG_E_INVALID;
+    }
+    return MP2VG_OK;
+}
+
+// ---- items (include/mp2vg.h "Items"); host only ----------------------------------------------------
+
+static_assert(sizeof(mp2vg_tensor_item_t) == 32, "ABI: struct sizes");
+static constexpr int32_t kTensorMaxItems = 65535;  // the item index is a grid dimension
+
+// One table of an items launch as it lies in the blob: the horizontal one of a src_w (segs, hfirst,
+// hw) or the vertical one of a src_h (vfirst, vcount, vw), built by tensor_tables from a rectangle
+// whose other side is 1 (the sides' tables do not depend on each other).
+struct ItemsTable {
+    int32_t src, off[3], nsegs, maxc;
+};
+
+int tensor_items_plan(const mp2vg_tensor_t* t, const mp2vg_tensor_item_t* items, int32_t n, int32_t clip_len, int32_t cf,
+                      int32_t coded_w, int32_t coded_h, int32_t nslots, bool planes, ItemsPlan* plan) {
+    if (!t || !items) return MP2VG_E_INVALID;
+    if (n < 1 || n > kTensorMaxItems) {
+        set_error("tensor items: n outside 1 .. 65535");
+        return MP2VG_E_INVALID;
+    }
+    if (t->src_x || t->src_y || t->src_w || t->src_h) {
+        set_error("tensor items: t->src_* must be 0 (the rectangles come from the items)");
+        return MP2VG_E_INVALID;
+    }
+    if (clip_len < 1 || n % clip_len) {
+        set_error("tensor items: clip_len must be at least 1 and divide n");
+        return MP2VG_E_INVALID;
+    }
+    // everything of t but its rectangle, by the check of the other entry points: over a rectangle
+    // of one pixel, which every coded frame holds and every output size may be made from
+    mp2vg_tensor_t t1 = *t;
+    t1.src_w = t1.src_h = 1;
+    int32_t rect[4];
+    if (int rc = check_tensor(&t1, coded_w, coded_h, rect, &plan->elem)) return rc;
+    auto bad = [](int32_t i, const char* why) {
+        set_error("tensor items: item " + std::to_string(i) + ": " + why);
+        return MP2VG_E_INVALID;
+    };
+    for (int32_t i = 0; i < n; i++) {
+        const mp2vg_tensor_item_t& it = items[i];
+        const bool whole = !it.src_w && !it.src_h;
+        const int64_t sw = whole ? coded_w : it.src_w, sh = whole ? coded_h : it.src_h;
+        if (it.flags & ~MP2VG_ITEM_HFLIP) return bad(i, "unknown flag bit");
+        if (it.reserved) return bad(i, "reserved is not 0");
+        if (planes ? it.slot != 0 : it.slot < 0 || (nslots >= 0 && it.slot >= nslots))
+            return bad(i, planes ? "slot must be 0 in the planes call" : "slot out of range");
+        if (check_tensor_field(it.field, cf, coded_h) != MP2VG_OK)
+            return bad(i, it.field < MP2VG_FIELD_PROGRESSIVE || it.field > MP2VG_FIELD_WEAVE
+                              ? "field mode outside MP2VG_FIELD_*"
+                              : "a field mode needs an even coded height (4:2:0: a multiple of 4)");
+        if (it.src_x < 0 || it.src_y < 0 || sw < 1 || sh < 1 || (whole && (it.src_x || it.src_y)) ||
+            it.src_x + sw > coded_w || it.src_y + sh > coded_h)
+            return bad(i, "bad source rectangle");
+        if (sw > 32 * (int64_t)t->out_w || sh > 32 * (int64_t)t->out_h) return bad(i, "bad ratio (above 32)");
+    }
+    // the distinct sizes in order of first use, then their tables behind the records
+    std::vector<ItemsTable> tab[2];
+    plan->htab.resize(n), plan->vtab.resize(n);
+    for (int32_t i = 0; i < n; i++)
+        for (int ax = 0; ax < 2; ax++) {
+            const int32_t src = ax ? (items[i].src_h ? items[i].src_h : coded_h) : (items[i].src_w ? items[i].src_w : coded_w);
+            size_t k = 0;
+            while (k < tab[ax].size() && tab[ax][k].src != src) k++;
+            if (k == tab[ax].size()) tab[ax].push_back(ItemsTable{src, {0, 0, 0}, 0, 0});
+            (ax ? plan->vtab : plan->htab)[i] = (int32_t)k;
+        }
+    std::vector<int32_t>& b = plan->blob;
+    b.assign((size_t)n * kItemWords, 0);
+    for (int ax = 0; ax < 2; ax++)
+        for (ItemsTable& e : tab[ax]) {
+            const int32_t r[4] = {0, 0, ax ? 1 : e.src, ax ? e.src : 1};
+            TensorTables tt;
+            if (int rc = tensor_tables(r, ax ? 1 : t->out_w, ax ? t->out_h : 1, 0, &tt)) return rc;
+            const size_t from = tt.off[ax ? 3 : 0], to = ax ? tt.blob.size() : tt.off[3];
+            if (b.size() + (to - from) > (size_t)INT32_MAX) {
+                set_error("tensor items: the tables of the launch exceed 2^31 words (too many distinct sizes)");
+                return MP2VG_E_INVALID;
+            }
+            for (int k = 0; k < 3; k++) e.off[k] = (int32_t)(b.size() + tt.off[(ax ? 3 : 0) + k] - from);
+            e.nsegs = tt.nsegs, e.maxc = ax ? tt.vmax : tt.hmax;
+            b.insert(b.end(), tt.blob.begin() + from, tt.blob.begin() + to);
+        }
+    plan->nh = (int32_t)tab[0].size(), plan->nv = (int32_t)tab[1].size(), plan->grid_x = 0;
+    const bool planar = t->layout == MP2VG_EXPORT_RGB_PLANAR;
+    for (int32_t i = 0; i < n; i++) {
+        const ItemsTable &h = tab[0][plan->htab[i]], &v = tab[1][plan->vtab[i]];
+        int32_t* r = b.data() + (size_t)i * kItemWords;
+        r[kItemSlot] = items[i].slot, r[kItemField] = items[i].field;
+        r[kItemSrcX] = items[i].src_x, r[kItemSrcY] = items[i].src_y, r[kItemFlags] = items[i].flags;
+        r[kItemNsegs] = h.nsegs, r[kItemHmax] = h.maxc, r[kItemVmax] = v.maxc;
+        r[kItemSegs] = h.off[0], r[kItemHfirst] = h.off[1], r[kItemHw] = h.off[2];
+        r[kItemVfirst] = v.off[0], r[kItemVcount] = v.off[1], r[kItemVw] = v.off[2];
+        r[kItemPlane] = planar ? i / clip_len * 3 * clip_len + i % clip_len : 3 * i;
+        plan->grid_x = std::max(plan->grid_x, h.nsegs);
+    }
+    return MP2VG_OK;
+}
 }  // namespace mp2vg
+
+extern "C" int mp2vg_tensor_items_plan(const mp2vg_config_t* cfg, const mp2vg_tensor_t* t,
+                                       const mp2vg_tensor_item_t* items, int32_t n, int32_t clip_len, int32_t* htab,
+                                       int32_t* vtab, int32_t summary[4]) {
+    int32_t w[3], h[3];
+    if (!cfg || !summary || mp2vg_frame_geometry(cfg, w, h, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
+    ItemsPlan plan;
+    if (int rc = tensor_items_plan(t, items, n, clip_len, cfg->chroma_format, w[0], h[0], -1, false, &plan)) return rc;
+    if (htab) memcpy(htab, plan.htab.data(), sizeof(int32_t) * n);
+    if (vtab) memcpy(vtab, plan.vtab.data(), sizeof(int32_t) * n);
+    summary[0] = plan.nh, summary[1] = plan.nv, summary[2] = plan.grid_x, summary[3] = (int32_t)plan.blob.size();
+    return MP2VG_OK;
+}
 
 extern "C" int mp2vg_tensor_bytes(const mp2vg_config_t* cfg, const mp2vg_tensor_t* t, int32_t n, uint64_t* bytes) {
     if (!cfg || !bytes || n <= 0 || mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK)

@@ -38,10 +38,19 @@
 // picture rows of the pair only (none: skipped), and the horizontal pass writes the pad through the
 // same normalise / cast as the picture (comments at both).
 //
+// Items (mp2vg_tensor_items, include/mp2vg.h "Items"): a fourth instantiation, ITEMS = true, always
+// with the field row walk and never placed, so the three above keep their code (they read every
+// argument where they read it before).  blockIdx.z is the item; its record (tensor_kernel.h: slot,
+// mode, rectangle origin, where its tables lie, their nsegs / hmax / vmax, the mirror flag, its
+// first output plane) is loaded once with scalar loads and stays in SGPRs.  The grid has the
+// launch's largest segment count: a workgroup past its item's returns before the barrier.  The
+// mirror and the clip layout change the store address only (comment at the store).
+//
 // Static resources (hipcc -O3, --offload-arch=gfx950, 40 variants each): 60-68 VGPRs without
-// field modes, 65-72 with, 65-74 placed, no scratch, 24576 B LDS per workgroup, which sets 6 waves
+// field modes, 65-72 with, 65-74 placed, 65-72 items (72-86 SGPRs, the field kernel's 66-80 plus
+// the record), no scratch, 24576 B LDS per workgroup, which sets 6 waves
 // per SIMD (up to 80 VGPRs keep that; measured speed, also of the one-row split this replaced:
-// profiles/export/tensor.md).
+// profiles/export/tensor.md; of the items launch: profiles/export/items.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -123,19 +132,47 @@ __device__ __forceinline__ uint16_t bf16_rne(float f) {
 // frame's MP2VG_FIELD_* mode picks the row walk of the vertical pass.
 // PLACED = true (with FIELDS = true only): out_w x out_h is a canvas, the tables are those of the
 // picture's rectangle dst_w x dst_h in it and everything outside the rectangle is the pad colour.
-template <int CF, bool LINEAR, bool PACKED, int DTYPE, bool FIELDS, bool PLACED>
+// ITEMS = true (with FIELDS = true, PLACED = false only): frame f is item f of the launch; its
+// slot, mode, rectangle origin, tables and mirror flag come from its record (tensor_kernel.h).
+template <int CF, bool LINEAR, bool PACKED, int DTYPE, bool FIELDS, bool PLACED, bool ITEMS>
 __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     static_assert(FIELDS || !PLACED, "the placed kernel rides the field row walk");
+    static_assert(!ITEMS || (FIELDS && !PLACED), "the items kernel rides the field row walk and is never placed");
     __shared__ alignas(8) int16_t lds[2][3][kTensorSegCols];
     const int tid = (int)threadIdx.x;
     const int oy = 2 * (int)blockIdx.y;         // output rows oy and, unless oy is the last, oy + 1
     const bool two = oy + 1 < a.out_h;
     const size_t f = blockIdx.z;
-    const int32_t* seg = a.segs + 4 * blockIdx.x;
+    // Items: the record is uniform over the workgroup, loaded once and kept scalar (readfirstlane, as
+    // for the mode below), so the origin, the table pointers, hmax, vmax and the flip flag stay in
+    // SGPRs.  A workgroup at or beyond its item's segment count (the grid has the launch's largest)
+    // returns here, whole, so the barrier below stays uniform.
+    const int32_t* rec = ITEMS ? a.items + (size_t)kItemWords * f : nullptr;
+    auto item = [&](int k) { return __builtin_amdgcn_readfirstlane(rec[k]); };
+    if (ITEMS && (int)blockIdx.x >= item(kItemNsegs)) return;
+    const int i_src_x = ITEMS ? item(kItemSrcX) : 0, i_src_y = ITEMS ? item(kItemSrcY) : 0;
+    const int i_hmax = ITEMS ? item(kItemHmax) : 0, i_vmax = ITEMS ? item(kItemVmax) : 0;
+    const bool flip = ITEMS && (item(kItemFlags) & MP2VG_ITEM_HFLIP);
+    const int plane0 = ITEMS ? item(kItemPlane) : 0;
+    const int32_t* i_segs = ITEMS ? a.items + item(kItemSegs) : nullptr;
+    const int32_t* i_hfirst = ITEMS ? a.items + item(kItemHfirst) : nullptr;
+    const int32_t* i_hw = ITEMS ? a.items + item(kItemHw) : nullptr;
+    const int32_t* i_vfirst = ITEMS ? a.items + item(kItemVfirst) : nullptr;
+    const int32_t* i_vcount = ITEMS ? a.items + item(kItemVcount) : nullptr;
+    const int32_t* i_vw = ITEMS ? a.items + item(kItemVw) : nullptr;
+    // the record's value in the items kernel, else the argument, read where it is used (which keeps
+    // the code of the other kernels as it was)
+#define ARG(name) (ITEMS ? i_##name : a.name)
+    const int32_t* seg = ARG(segs) + 4 * blockIdx.x;
     const int o_begin = seg[0], o_end = seg[1], base = seg[2], nunits = seg[3];
     const uint8_t* pl[3];
 #pragma unroll
-    for (int p = 0; p < 3; p++) pl[p] = a.slots ? (const uint8_t*)a.ftab[a.slots[f]] + a.plane_off[p] : a.planes[p];
+    for (int p = 0; p < 3; p++) {
+        if (ITEMS)
+            pl[p] = a.ftab ? (const uint8_t*)a.ftab[item(kItemSlot)] + a.plane_off[p] : a.planes[p];
+        else
+            pl[p] = a.slots ? (const uint8_t*)a.ftab[a.slots[f]] + a.plane_off[p] : a.planes[p];
+    }
 
     // vertical pass over the union of the two rows' source rows (vfirst and the range ends never
     // decrease with the output row); a row outside one output row's taps has weight 0 there
@@ -147,21 +184,21 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     // union is the picture row's range) and reads the weights of a row that exists.
     bool pic0 = true, pic1 = two;
     if (!PLACED) {
-        f0 = a.vfirst[oy], c0 = a.vcount[oy];
-        f1 = two ? a.vfirst[oy + 1] : f0, c1 = two ? a.vcount[oy + 1] : 0;
+        f0 = ARG(vfirst)[oy], c0 = ARG(vcount)[oy];
+        f1 = two ? ARG(vfirst)[oy + 1] : f0, c1 = two ? ARG(vcount)[oy + 1] : 0;
         nrows = max(f0 + c0, f1 + c1) - f0;
-        qv0 = a.vw + (size_t)oy * a.vmax;
-        qv1 = qv0 + (two ? a.vmax : 0);
+        qv0 = ARG(vw) + (size_t)oy * ARG(vmax);
+        qv1 = qv0 + (two ? ARG(vmax) : 0);
     } else {
         const int r0 = oy - a.dst_y;
         pic0 = r0 >= 0 && r0 < a.dst_h;
         pic1 = two && r0 + 1 >= 0 && r0 + 1 < a.dst_h;
         const int ra = pic0 ? r0 : pic1 ? r0 + 1 : 0, rb = pic1 ? r0 + 1 : ra;  // rows inside the tables
-        f0 = a.vfirst[ra], c0 = pic0 ? a.vcount[ra] : 0;
-        f1 = pic1 ? a.vfirst[rb] : f0, c1 = pic1 ? a.vcount[rb] : 0;
+        f0 = ARG(vfirst)[ra], c0 = pic0 ? ARG(vcount)[ra] : 0;
+        f1 = pic1 ? ARG(vfirst)[rb] : f0, c1 = pic1 ? ARG(vcount)[rb] : 0;
         nrows = max(f0 + c0, f1 + c1) - f0;
-        qv0 = a.vw + (size_t)ra * a.vmax;
-        qv1 = a.vw + (size_t)rb * a.vmax;
+        qv0 = ARG(vw) + (size_t)ra * ARG(vmax);
+        qv1 = ARG(vw) + (size_t)rb * ARG(vmax);
     }
     // field modes (uniform over the workgroup).  WEAVE and PROGRESSIVE walk every row of the union
     // as above, with the line's own chroma siting.  TOP / BOTTOM (parity par) walk only the field's
@@ -173,10 +210,11 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     // (readfirstlane: the choice between the list and the argument is a vector load to the compiler;
     // as a scalar the mode keeps the walk's bounds, rows and weights in SGPRs)
     const int mode = !FIELDS ? MP2VG_FIELD_PROGRESSIVE
-                             : __builtin_amdgcn_readfirstlane(a.fields ? a.fields[f] : a.field);
+                : ITEMS ? item(kItemField)
+                        : __builtin_amdgcn_readfirstlane(a.fields ? a.fields[f] : a.field);
     const bool single = mode == MP2VG_FIELD_TOP || mode == MP2VG_FIELD_BOTTOM;
     const int par = mode == MP2VG_FIELD_BOTTOM ? 1 : 0;
-    const int Y0 = a.src_y + f0, Yl = Y0 + nrows - 1;
+    const int Y0 = ARG(src_y) + f0, Yl = Y0 + nrows - 1;
     const int z0 = single ? max(Y0 - ((Y0 & 1) != par ? 1 : 0), par) : Y0;
     const int z1 = single ? Yl + ((Yl & 1) != par ? 1 : 0) : Yl;
     const int zmax = single ? a.coded_h - 2 + par : Yl;
@@ -184,20 +222,20 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
     // weight of row k of the union for the two output rows: the loads are unconditional (the index
     // clamped into the row's vmax entries), so the scalar loads of one line issue together
     auto wt0 = [&](int k) {
-        const int q = qv0[min(max(k, 0), a.vmax - 1)];
+        const int q = qv0[min(max(k, 0), ARG(vmax) - 1)];
         return k >= 0 && k < c0 ? q : 0;
     };
     auto wt1 = [&](int k) {
-        const int q = qv1[min(max(k + f0 - f1, 0), a.vmax - 1)];
+        const int q = qv1[min(max(k + f0 - f1, 0), ARG(vmax) - 1)];
         return k + f0 - f1 >= 0 && k + f0 - f1 < c1 ? q : 0;
     };
     // (a workgroup whose rows are both pad has no vertical pass; the barrier below stays uniform)
     for (int u = tid; u < (!PLACED || pic0 || pic1 ? nunits : 0); u += 256) {
-        const int x0 = a.src_x + base + 4 * u;
+        const int x0 = ARG(src_x) + base + 4 * u;
         int aR[2][4] = {}, aG[2][4] = {}, aB[2][4] = {};
         if (!FIELDS) {
             for (int k = 0; k < nrows; k++) {
-                const int y = a.src_y + f0 + k;
+                const int y = ARG(src_y) + f0 + k;
                 Rows r;
                 const int j = CF == 1 ? y >> 1 : y;
                 const int j1 = CF == 1 && LINEAR ? min(max(j + ((y & 1) ? 1 : -1), 0), a.ch - 1) : j;
@@ -312,18 +350,23 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
             // the table's rows are zero from the column's tap count on, and a V index past the window is clamped (its
             // weight is zero, whatever the LDS holds there)
             const int16_t* v = &lds[t][c][0];
-            const int v0 = a.hfirst[op] - base;
-            const int32_t* qh = a.hw + (size_t)op * a.hmax;
+            const int v0 = ARG(hfirst)[op] - base;
+            const int32_t* qh = ARG(hw) + (size_t)op * ARG(hmax);
             int sum = 8192;
 #pragma unroll 4
-            for (int k = 0; k < a.hmax; k++) sum += __mul24(qh[k], (int)v[min(v0 + k, kTensorSegCols - 1)]);
+            for (int k = 0; k < ARG(hmax); k++) sum += __mul24(qh[k], (int)v[min(v0 + k, kTensorSegCols - 1)]);
             Q = sum >> 14;
         } else {
             Q = c == 0 ? a.padq[0] : c == 1 ? a.padq[1] : a.padq[2];  // through the same normalise and cast below
         }
         const size_t y = (size_t)(oy + t);
-        const size_t at = PACKED ? ((f * h + y) * w + (size_t)o) * 3 + (size_t)c
-                                 : ((f * 3 + (size_t)c) * h + y) * w + (size_t)o;
+        // Items: a flipped item's segment writes the mirrored run of columns (the mirror is an index
+        // reversal behind both passes; every element still has exactly one writer), and the planar
+        // address is the clip layout's: plane kItemPlane + c clip_len of h x w elements.
+        const size_t ox = (size_t)(ITEMS && flip ? a.out_w - 1 - o : o);
+        const size_t at = PACKED  ? ((f * h + y) * w + ox) * 3 + (size_t)c
+                          : ITEMS ? ((size_t)(plane0 + c * a.clip_len) * h + y) * w + ox
+                                  : ((f * 3 + (size_t)c) * h + y) * w + ox;
         if (DTYPE == MP2VG_TENSOR_U8) {
             ((uint8_t*)a.dst)[at] = (uint8_t)((Q + 32) >> 6);
         } else {
@@ -339,37 +382,38 @@ __global__ __launch_bounds__(256) void tensor_kernel(const TensorArgs a) {
         }
     }
 }
+#undef ARG
 
-template <int CF, bool LINEAR, bool PACKED, bool FIELDS, bool PLACED>
+template <int CF, bool LINEAR, bool PACKED, bool FIELDS, bool PLACED, bool ITEMS = false>
 static void launch_dtype(int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
     const dim3 block(256, 1, 1);
     if (dtype == MP2VG_TENSOR_U8)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8, FIELDS, PLACED>), grid, block, 0, stream,
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_U8, FIELDS, PLACED, ITEMS>), grid, block, 0, stream,
                            a);
     else if (dtype == MP2VG_TENSOR_F16)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16, FIELDS, PLACED>), grid, block, 0, stream,
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F16, FIELDS, PLACED, ITEMS>), grid, block, 0, stream,
                            a);
     else if (dtype == MP2VG_TENSOR_BF16)
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16, FIELDS, PLACED>), grid, block, 0,
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_BF16, FIELDS, PLACED, ITEMS>), grid, block, 0,
                            stream, a);
     else
-        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32, FIELDS, PLACED>), grid, block, 0, stream,
+        hipLaunchKernelGGL((tensor_kernel<CF, LINEAR, PACKED, MP2VG_TENSOR_F32, FIELDS, PLACED, ITEMS>), grid, block, 0, stream,
                            a);
 }
 
-template <int CF, bool FIELDS, bool PLACED>
+template <int CF, bool FIELDS, bool PLACED, bool ITEMS = false>
 static void launch_cf(int layout, int chroma, int dtype, const TensorArgs& a, dim3 grid, hipStream_t stream) {
     const bool lin = chroma == MP2VG_EXPORT_CHROMA_LINEAR && CF != 3;  // 4:4:4: LINEAR is NEAREST
     if (layout == MP2VG_EXPORT_RGB_PACKED) {
         if (lin)
-            launch_dtype<CF, CF != 3, true, FIELDS, PLACED>(dtype, a, grid, stream);
+            launch_dtype<CF, CF != 3, true, FIELDS, PLACED, ITEMS>(dtype, a, grid, stream);
         else
-            launch_dtype<CF, false, true, FIELDS, PLACED>(dtype, a, grid, stream);
+            launch_dtype<CF, false, true, FIELDS, PLACED, ITEMS>(dtype, a, grid, stream);
     } else {
         if (lin)
-            launch_dtype<CF, CF != 3, false, FIELDS, PLACED>(dtype, a, grid, stream);
+            launch_dtype<CF, CF != 3, false, FIELDS, PLACED, ITEMS>(dtype, a, grid, stream);
         else
-            launch_dtype<CF, false, false, FIELDS, PLACED>(dtype, a, grid, stream);
+            launch_dtype<CF, false, false, FIELDS, PLACED, ITEMS>(dtype, a, grid, stream);
     }
 }
 
@@ -394,6 +438,18 @@ hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_m
         launch_walk<2>(layout, chroma, dtype, field_modes, placed, a, grid, stream);
     else
         launch_walk<3>(layout, chroma, dtype, field_modes, placed, a, grid, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_tensor_items(int cf, int layout, int chroma, int dtype, const TensorArgs& a, int nsegs, int n,
+                               hipStream_t stream) {
+    const dim3 grid((unsigned)nsegs, (unsigned)((a.out_h + 1) / 2), (unsigned)n);
+    if (cf == 1)
+        launch_cf<1, true, false, true>(layout, chroma, dtype, a, grid, stream);
+    else if (cf == 2)
+        launch_cf<2, true, false, true>(layout, chroma, dtype, a, grid, stream);
+    else
+        launch_cf<3, true, false, true>(layout, chroma, dtype, a, grid, stream);
     return hipGetLastError();
 }
 

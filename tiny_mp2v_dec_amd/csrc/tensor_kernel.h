@@ -46,6 +46,22 @@ struct TensorArgs {
     // out_w x out_h canvas; the tables are then those of dst_w x dst_h.  padq[c] = 64 pad[c].
     int32_t dst_x, dst_y, dst_w, dst_h;
     int32_t padq[3];
+    // items, behind those (read by the items kernel only): the staged blob, which starts with the n
+    // item records (kItem* below) and holds the shared tap tables behind them; every table of an
+    // item is found at items + the record's offset.  The pointers and counts above that a record
+    // replaces (slots, fields, src_x / src_y, the six tables, hmax, vmax) are not read.
+    const int32_t* items;
+    int32_t clip_len;  // planar layout [n / clip_len][3][clip_len][h][w]
+};
+
+// One item of an items launch as the kernel reads it: kItemWords int32 words.  Offsets are in words
+// from the start of the blob.  kItemPlane is the planar plane index of channel 0,
+// (i / clip_len) 3 clip_len + i % clip_len (channel c is clip_len planes further), so the kernel
+// divides nothing.
+enum {
+    kItemSlot = 0, kItemField, kItemSrcX, kItemSrcY, kItemFlags, kItemNsegs, kItemHmax, kItemVmax,
+    kItemSegs, kItemHfirst, kItemHw, kItemVfirst, kItemVcount, kItemVw, kItemPlane, kItemSpare,
+    kItemWords
 };
 
 // cf 1..3; layout, chroma, dtype of the mp2vg_tensor_t; grid = (nsegs, row pairs of out_h, n).
@@ -53,6 +69,10 @@ struct TensorArgs {
 // placed = true: the placed kernel (always with the field row walk, whatever field_modes says).
 hipError_t launch_tensor(int cf, int layout, int chroma, int dtype, bool field_modes, bool placed, const TensorArgs& a,
                          int nsegs, int n, hipStream_t stream);
+// the items kernel (always with the field row walk, never placed); nsegs = the largest segment
+// count of any item: a workgroup past its item's count returns at once
+hipError_t launch_tensor_items(int cf, int layout, int chroma, int dtype, const TensorArgs& a, int nsegs, int n,
+                               hipStream_t stream);
 
 // host-only side (runtime.cpp)
 // checks t against a coded size; the source rectangle in rect[4] (x, y, w, h) and the element size
@@ -70,5 +90,17 @@ struct TensorTables {
     int32_t nsegs, hmax, vmax;
 };
 int tensor_tables(const int32_t rect[4], int32_t out_w, int32_t out_h, size_t lead, TensorTables* tt);
+// a field mode's preconditions on the coded frame (include/mp2vg.h "Field modes")
+int check_tensor_field(int32_t field, int32_t cf, int32_t coded_h);
+
+// An items launch (include/mp2vg.h "Items"), validated and planned with no device.  nslots < 0:
+// the slot count is not known (mp2vg_tensor_items_plan); planes: every slot must be 0.
+struct ItemsPlan {
+    std::vector<int32_t> blob;        // n records of kItemWords, the horizontal tables, the vertical tables
+    std::vector<int32_t> htab, vtab;  // per item: its table, numbered in order of first use
+    int32_t nh, nv, grid_x, elem;
+};
+int tensor_items_plan(const mp2vg_tensor_t* t, const mp2vg_tensor_item_t* items, int32_t n, int32_t clip_len, int32_t cf,
+                      int32_t coded_w, int32_t coded_h, int32_t nslots, bool planes, ItemsPlan* plan);
 
 }  // namespace mp2vg

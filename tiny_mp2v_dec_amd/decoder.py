@@ -140,6 +140,26 @@ class frame_c:  # noqa: N801  (reference name)
                   "tensor_planes_placed")
         return o
 
+    def export_items(self, crops, size, flips=None, fields=None, clip_len=1, dtype="float16", mean=None, std=None,
+                     layout="nchw", chroma="linear", matrix=1, out=None):
+        """One image per rectangle of this frame in one kernel launch (mp2vg_tensor_planes_items;
+        arguments and result as DeviceContext.export_items, every item reading this frame): the
+        boxes of a detector cropped from the full-resolution frame and resized for the next stage.
+        Device frames only; complete on return, so the tensor outlives the callback."""
+        if not self.is_device:
+            raise ValueError("host frame: export_items needs a device_frames=True decoder")
+        f = self._f
+        cf = 3 if f.width[1] == f.width[0] else (2 if f.height[1] == f.height[0] else 1)
+        items = _lib.make_items(None, crops, flips, fields, len(crops))
+        t = _lib.make_tensor(size, None, dtype, mean, std, layout, chroma, matrix)
+        o = _lib.tensor_out(out, _lib.items_shape(t, len(items), int(clip_len)), dtype, f.device)
+        planes = (ctypes.c_void_p * 3)(*[self.device_ptr(i) for i in range(3)])
+        check(lib().mp2vg_tensor_planes_items(f.device, planes, f.stride, cf, f.width[0], f.height[0], items,
+                                              len(items), ctypes.byref(t), int(clip_len),
+                                              ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()),
+              "tensor_planes_items")
+        return o
+
     def get_strides(self, i):
         return self._f.stride[i]
 

@@ -435,6 +435,28 @@ class DeviceContext:
             self.synchronize()
         return o
 
+    def export_items(self, slots, size, crops, flips=None, fields=None, clip_len=1, dtype="float16", mean=None,
+                     std=None, layout="nchw", chroma="linear", matrix=1, out=None, sync=True):
+        """One image per item in one kernel launch (mp2vg_tensor_items, include/mp2vg.h "Items"):
+        item i is frame slots[i] (any order, repeats allowed) in field mode fields[i], cropped to
+        crops[i] = (x, y, w, h) in luma pixels (None: the coded frame), resized to size = (width,
+        height), mirrored left to right when flips[i], then normalised and cast as export_tensor
+        does (dtype, mean, std, chroma, matrix as there).  slots, flips and fields also take one
+        value for every item (_lib.make_items).  The random-resized-crop and flip of every sample
+        of a batch, or every box of a detector, is one call.
+        (n, 3, h, w) for layout "nchw", (n, h, w, 3) for "nhwc"; with clip_len = T > 1 the planar
+        result is (n / T, 3, T, h, w), the clip layout of video models: item i is frame i % T of
+        clip i / T.  Writes into `out` when given.  Stream ordering, sync and the limit of 65535
+        items per call as export_tensor."""
+        items = _lib.make_items(slots, crops, flips, fields)
+        t = _lib.make_tensor(size, None, dtype, mean, std, layout, chroma, matrix)
+        o = _lib.tensor_out(out, _lib.items_shape(t, len(items), int(clip_len)), dtype, self.cfg.device)
+        check(lib().mp2vg_tensor_items(self.h, items, len(items), ctypes.byref(t), int(clip_len),
+                                       ctypes.c_void_p(o.data_ptr()), o.numel() * o.element_size()), "tensor_items")
+        if sync:
+            self.synchronize()
+        return o
+
     def digests(self, slots):
         slots = np.ascontiguousarray(slots, np.int32)
         out = np.zeros(len(slots), np.uint64)
@@ -498,6 +520,28 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
                            sync=False)
         ctx.synchronize()
         return out
+
+
+def items_plan(width, height, chroma_format, size, crops, flips=None, fields=None, clip_len=1, slots=0, dtype="float16",
+               layout="nchw", items=None):
+    """What an items launch (DeviceContext.export_items) stages and launches, with no device
+    (mp2vg_tensor_items_plan): a dict of htab / vtab (the tap table of each item per axis, tables
+    numbered in order of first use), n_htab / n_vtab (distinct tables), grid_x (the largest segment
+    count of any item) and words (int32 words staged: the item records, then the tables).  Raises
+    Mp2vgError where the launch would be refused.  items: a ready (_lib.Item * n) array instead of
+    slots / crops / flips / fields."""
+    if items is None:
+        items = _lib.make_items(slots, crops, flips, fields)
+    n = len(items)
+    cfg = _lib.make_config(width, height, chroma_format)
+    t = _lib.make_tensor(size, None, dtype, layout=layout)
+    htab, vtab, summary = np.zeros(n, np.int32), np.zeros(n, np.int32), (ctypes.c_int32 * 4)()
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    check(lib().mp2vg_tensor_items_plan(ctypes.byref(cfg), ctypes.byref(t), items, n, int(clip_len),
+                                        htab.ctypes.data_as(i32p), vtab.ctypes.data_as(i32p), summary),
+          "tensor_items_plan")
+    return {"htab": htab, "vtab": vtab, "n_htab": summary[0], "n_vtab": summary[1], "grid_x": summary[2],
+            "words": summary[3]}
 
 
 def field_plan(display, flags, fields):
