@@ -213,7 +213,9 @@ int  mp2vg_last_launch_times(mp2vg_ctx_t* ctx, float* ms, int32_t max, int32_t* 
 int  mp2vg_last_batch_time(mp2vg_ctx_t* ctx, float* ms);
 /* times of the batch decoded `back` decodes ago (0 = the last; the last 64 are kept), so batches
  * can be decoded back to back and timed afterwards: whole-batch span (batch_ms, may be NULL) and
- * per-launch device times (launch_ms[0..min(count, max)), may be NULL); synchronises */
+ * per-launch device times (launch_ms[0..min(count, max)), may be NULL); synchronises.  A decode
+ * that ran the placement calibration (below) counts as one batch: its times are those of one
+ * run on the pool that was kept. */
 int  mp2vg_batch_times(mp2vg_ctx_t* ctx, int32_t back, float* batch_ms, float* launch_ms, int32_t max,
                        int32_t* count);
 /* device time (ms) from the start of the batch decoded `back_first` decodes ago to the end of the
@@ -235,7 +237,11 @@ int  mp2vg_copy_slot_packed(mp2vg_ctx_t* ctx, int32_t slot, void* dst, int32_t d
  * mp2vg_invalidate_slot, which makes the next decode that reads the slot rebuild its tiles.
  * The pointer can change once, at the context's first mp2vg_batch_decode, when the pool's
  * placement calibration keeps a copy of the pool (mp2vg_pool_placement; contents are carried
- * over): fetch it after that decode, or turn the calibration off (MP2VG_PLACE_CANDIDATES=1). */
+ * over): fetch it after that decode, or turn the calibration off (MP2VG_PLACE_CANDIDATES=1).
+ * Whether to calibrate is decided at that first decode alone: a context whose first batch was
+ * not calibrated (pool below MP2VG_PLACE_MIN_MB, or a batch that overwrites a slot it read from
+ * before it) never is, also not after mp2vg_reserve_slots has grown the pool (which adds blocks
+ * and moves no slot). */
 int  mp2vg_slot_device_ptr(mp2vg_ctx_t* ctx, int32_t slot, void** dptr);
 /* the slot's frame was written by someone other than the decode (an RCCL receive, an external
  * producer writing through mp2vg_slot_device_ptr): its anchor tiles are stale.  The next batch

@@ -67,10 +67,14 @@ def mc(dst, src0, off0, src1, off1, stride, width, height, bidir, idx):
                     stride, width, height, bidir, idx)
 
 
-def reconstruct(width, height, chroma_format, pics, mbs, coefs, nslots):
-    """pics/mbs/coefs: numpy structured arrays / uint32 array (tiny_mp2v_dec_amd.records dtypes)."""
+def reconstruct(width, height, chroma_format, pics, mbs, coefs, nslots, pool=None):
+    """pics/mbs/coefs: numpy structured arrays / uint32 array (tiny_mp2v_dec_amd.records dtypes).
+    pool: the slots before the batch (slot_bytes * nslots + 64 bytes, decoded in place; default
+    zeros): oracle_reconstruct never clears the pool, so a preloaded slot is what its readers see."""
     g = geometry(width, height, chroma_format)
-    pool = np.zeros(int(g.slot_bytes) * nslots + 64, np.uint8)
+    if pool is None:
+        pool = np.zeros(int(g.slot_bytes) * nslots + 64, np.uint8)
+    assert pool.dtype == np.uint8 and pool.flags.c_contiguous and len(pool) == int(g.slot_bytes) * nslots + 64
     rc = lib().oracle_reconstruct(ctypes.byref(g), _ptr(pics), len(pics), _ptr(mbs), _ptr(coefs),
                                   _ptr(pool), nslots)
     if rc != 0:

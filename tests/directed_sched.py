@@ -32,14 +32,16 @@ REQUIREMENTS = ("cover", "hazard", "sets", "mode", "tiles", "foot")
 # ---- batches from picture specs ---------------------------------------------------------------
 # One picture: (type, dst, fwd, bwd, kind).  type "I" / "P" / "B"; kind says what its macroblocks
 # do: "i" all intra, "f" forward, "b" backward, "fb" every direction mix, "n" inter MBs that carry
-# neither direction flag (forward prediction by definition, P pictures).
+# neither direction flag (forward prediction by definition, P pictures), "d" both directions in every
+# inter MB (a two-direction B picture even where the picture is one MB).
 def pic(t, dst, fwd=-1, bwd=-1, kind=None):
     kind = kind or {"I": "i", "P": "f", "B": "fb"}[t]
     return (t, dst, fwd, bwd, kind)
 
 
-DIRS = {"f": [MB_FWD], "b": [MB_BWD], "fb": [MB_FWD, MB_BWD, MB_FWD | MB_BWD], "n": [0]}
-USES = {"i": (False, False), "f": (True, False), "b": (False, True), "fb": (True, True), "n": (True, False)}
+DIRS = {"f": [MB_FWD], "b": [MB_BWD], "fb": [MB_FWD, MB_BWD, MB_FWD | MB_BWD], "n": [0], "d": [MB_FWD | MB_BWD]}
+USES = {"i": (False, False), "f": (True, False), "b": (False, True), "fb": (True, True), "n": (True, False),
+        "d": (True, True)}
 
 
 def used_refs(pics, mbs):

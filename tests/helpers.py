@@ -25,6 +25,39 @@ def oracle_frames(parsed: Parsed):
     return frames
 
 
+class SlotOracle:
+    """The oracle's pool indexed by slot across batches, with slots that something other than a
+    decode filled: preload() puts visible planes into a slot (its padding is left as it is, the
+    oracle never reads it), decode() runs a batch on the pool as it stands, grow() adds zero slots."""
+
+    def __init__(self, width, height, cf, nslots):
+        self.width, self.height, self.cf, self.nslots = width, height, cf, nslots
+        self.g = _oracle.geometry(width, height, cf)
+        self.pool = np.zeros(int(self.g.slot_bytes) * nslots + 64, np.uint8)
+
+    def _plane(self, slot, p):
+        g, base = self.g, slot * int(self.g.slot_bytes)
+        return self.pool[base + g.plane_off[p]: base + g.plane_off[p] + g.stride[p] * g.ph[p]] \
+            .reshape(g.ph[p], g.stride[p])[:, :g.pw[p]]
+
+    def planes(self, slot):
+        return [self._plane(slot, p) for p in range(3)]
+
+    def preload(self, slot, planes):
+        for p in range(3):
+            self._plane(slot, p)[:] = planes[p]
+
+    def decode(self, pics, mbs, coefs):
+        _oracle.reconstruct(self.width, self.height, self.cf, np.ascontiguousarray(pics), mbs, coefs, self.nslots,
+                            pool=self.pool)
+
+    def grow(self, nslots):
+        assert nslots >= self.nslots
+        pool = np.zeros(int(self.g.slot_bytes) * nslots + 64, np.uint8)
+        pool[:int(self.g.slot_bytes) * self.nslots] = self.pool[:int(self.g.slot_bytes) * self.nslots]
+        self.pool, self.nslots = pool, nslots
+
+
 def yuv_md5(planes):
     h = hashlib.md5()
     for p in planes:

@@ -1338,6 +1338,10 @@ static int env_int(const char* name, int dflt) {
 // before the batch (TilePlan.ext_reads); other batches are decoded once, uncalibrated.
 static int calibrate_placement(mp2vg_ctx_t* c) {
     if (c->placed) return 1;
+    // decided once, at the context's first decode, whatever the outcome: a caller may cache slot
+    // pointers after that decode (include/mp2vg.h), so a pool that was too small then, or whose
+    // first batch could not be decoded twice, is never moved later (after mp2vg_reserve_slots, say)
+    c->placed = true;
     const int k = std::max(1, std::min(6, env_int("MP2VG_PLACE_CANDIDATES", 3)));
     size_t pool = 0;
     for (size_t b : c->chunk_bytes) pool += b;
@@ -1349,10 +1353,10 @@ static int calibrate_placement(mp2vg_ctx_t* c) {
         if (w.first >= 0 && w.first < c->nslots) written[w.first] = 1;
     for (const auto& r : bk.tiles.ext_reads)
         if (r.first >= 0 && r.first < c->nslots && written[r.first]) return 1;
-    c->placed = true;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t seq0 = c->seq;
     std::vector<PoolSet> cand;
     cand.push_back(pool_take(c));
     // candidates only while an eighth of the device (at least 8 GB) stays free beside them, so
@@ -1368,6 +1372,7 @@ static int calibrate_placement(mp2vg_ctx_t* c) {
     }
     const size_t n = cand.size();
     std::vector<float> ms(2 * n, 0.f);
+    std::vector<uint64_t> at(2 * n, seq0);  // batch sequence number of each timed run
     int rc = MP2VG_OK;
     auto run = [&](size_t i, float* t) -> int {
         if (pool_install(c, cand[i]) != hipSuccess) {
@@ -1385,6 +1390,7 @@ static int calibrate_placement(mp2vg_ctx_t* c) {
     for (int r = 0; r < 2 && rc == MP2VG_OK; r++)
         for (size_t i = 0; i < n && rc == MP2VG_OK; i++) {
             if (r == 0 && i > 0) c->tiles_ok = tiles0;  // a candidate's first decode starts from the batch's entry state
+            at[r * n + i] = c->seq;
             rc = run(i, &ms[r * n + i]);
         }
     size_t best = 0;
@@ -1412,6 +1418,14 @@ static int calibrate_placement(mp2vg_ctx_t* c) {
     if (rc != MP2VG_OK) {  // an error keeps the original pool (its batch status is returned)
         for (size_t i = 1; i < n; i++) pool_set_free(cand[i]);
         best = 0;
+    }
+    // The caller decoded one batch: the history keeps one timed run as that batch (the kept pool's
+    // second, or after an error the last run that completed) and the batch count goes up by one,
+    // so mp2vg_batch_times never reports the calibration's own runs, some of them on dropped pools
+    if (c->seq > seq0) {
+        const uint64_t keep = rc == MP2VG_OK ? at[n + best] : c->seq - 1;
+        if (keep != seq0) std::swap(c->hist[seq0 % mp2vg_ctx::kHist], c->hist[keep % mp2vg_ctx::kHist]);
+        c->seq = seq0 + 1;
     }
     HIPCHK(pool_install(c, cand[best]));
     c->place_ms = ms;

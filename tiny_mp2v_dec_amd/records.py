@@ -248,9 +248,23 @@ class DeviceContext:
         except Exception:
             pass
 
-    def reserve(self, slots):
-        check(lib().mp2vg_reserve_slots(self.h, slots), "reserve_slots")
-        self.nslots = max(self.nslots, slots)
+    def reserve(self, nslots):
+        """Grow the pool to nslots slots (mp2vg_reserve_slots): the slots it has keep their
+        addresses and contents, the new ones read as zero; never shrinks."""
+        check(lib().mp2vg_reserve_slots(self.h, int(nslots)), "reserve_slots")
+        self.nslots = max(self.nslots, int(nslots))
+
+    def slot_ptr(self, slot):
+        """Device address of a slot's frame (mp2vg_slot_device_ptr); after writing through it, call
+        invalidate(slot)."""
+        p = ctypes.c_void_p()
+        check(lib().mp2vg_slot_device_ptr(self.h, int(slot), ctypes.byref(p)), "slot_device_ptr")
+        return p.value
+
+    def invalidate(self, slot):
+        """The slot's frame was written from outside the decode (mp2vg_invalidate_slot): the next
+        batch that predicts from it rebuilds its anchor tiles first."""
+        check(lib().mp2vg_invalidate_slot(self.h, int(slot)), "invalidate_slot")
 
     def upload(self, pics, mbs, coefs):
         pics = np.ascontiguousarray(pics, PIC_DTYPE)
