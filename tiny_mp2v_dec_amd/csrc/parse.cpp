@@ -11,8 +11,11 @@
 // Where the reference has undefined behaviour the stream is rejected (MP2VG_E_UNSUPPORTED):
 // missing QME / partial loads, intra MBs with intra_vlc_format=0, field pictures, dual-prime,
 // slices not starting at column 0, skipped MBs in I pictures, MC reads outside the reference
-// planes, 4:4:4 with field DCT (reference writes blocks 10/11 outside the MB), concealment MVs in
-// P/B pictures, scalable extensions.
+// planes, 4:4:4 with field DCT (reference writes blocks 10/11 outside the MB), concealment MVs
+// (P/B pictures: the reference ignores the flag; I pictures: parse_modes leaves
+// motion_vector_count 0 for intra macroblocks, mb_decoder.cpp:364-367, so parse_motion_vectors
+// reads two field selects and two vectors, :512-517, where the stream holds one vector, and the
+// parse derails: the reference crashed on the directed stream), scalable extensions.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -297,12 +300,11 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
             fsel[1][s] = (int)br.read(1);
             return parse_mv(1, s);
         };
-        const bool cmv = h.concealment_motion_vectors && pct == 1;
-        if (mfwd || (intra && cmv))
+        // (no concealment vectors: pictures that carry them are rejected in pass 1)
+        if (mfwd)
             if (!parse_mvs(0)) FAIL(MP2VG_E_BITSTREAM, "bad motion_code");
         if (mbwd)
             if (!parse_mvs(1)) FAIL(MP2VG_E_BITSTREAM, "bad motion_code");
-        if (intra && cmv) br.skip(1);
 
         // PMV update + MC selection (mb_decoder.cpp:580-620)
         mp2vg_mb_t& m = row[x];
@@ -326,7 +328,7 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
                 }
             }
             bool no_mc_p = (pct == 2 && !intra && !mfwd);
-            if (intra || no_mc_p) {  // concealment is never on in P/B templates
+            if (intra || no_mc_p) {
                 memset(PMVs, 0, sizeof(PMVs));
                 memset(MVs, 0, sizeof(MVs));
                 field_mv = false;
@@ -774,11 +776,15 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
             set_error("concealment motion vectors in a P/B picture");
             return MP2VG_E_UNSUPPORTED;
         }
+        if (h.concealment_motion_vectors) {
+            set_error("concealment motion vectors in an I picture (the reference reads two field vectors)");
+            return MP2VG_E_UNSUPPORTED;
+        }
         if (h.pct == 2 && P.fwd < 0) { set_error("P picture without a reference"); return MP2VG_E_UNSUPPORTED; }
         // f_code of every direction the picture may code vectors for is 1..9 (0 is forbidden and
         // the reference would read f_code - 1 = -1 residual bits, mb_decoder.cpp:500-505)
         for (int s = 0; s < 2; s++) {
-            const bool used = (s == 0 && (h.pct != 1 || h.concealment_motion_vectors)) || (s == 1 && h.pct == 3);
+            const bool used = (s == 0 && h.pct != 1) || (s == 1 && h.pct == 3);
             for (int t = 0; t < 2 && used; t++)
                 if (h.f_code[s][t] < 1 || h.f_code[s][t] > 9) {
                     set_error("f_code outside 1..9 for a direction the picture codes vectors for");

@@ -436,9 +436,9 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
         // motion_vectors
         int16_t MVs[2][2][2] = {};
         int fsel[2][2] = {};
-        const bool cmv = h.concealment_motion_vectors && pct == 1;
+        // (no concealment vectors: the scan rejects pictures that carry them)
         for (int s = 0; s < 2; s++) {
-            if (!(s == 0 ? (mfwd || (intra && cmv)) : mbwd)) continue;
+            if (!(s == 0 ? mfwd : mbwd)) continue;
             for (int r = 0; r < mv_count; r++) {
                 if (mv_count == 2 || field_mv) fsel[r][s] = (int)br.read(1);
                 for (int t = 0; t < 2; t++) {
@@ -455,7 +455,6 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
                 }
             }
         }
-        if (intra && cmv) br.skip(1);
 
         // PMV update + MC selection
         mp2vg_mb_t m;
