@@ -570,6 +570,60 @@ int  mp2vg_tensor_items_plan(const mp2vg_config_t* cfg, const mp2vg_tensor_t* t,
                              const mp2vg_tensor_item_t* items, int32_t n, int32_t clip_len,
                              int32_t* htab, int32_t* vtab, int32_t summary[4]);
 
+/* ---- motion export -----------------------------------------------------------------------
+ * The compressed domain as tensors: the motion field and the coded residual's activity on the
+ * macroblock grid, read from the resident record batch (mp2vg_batch_upload or
+ * mp2vg_batch_upload_es) and not from the frame slots, so no decode is needed (motion.hip).  All
+ * arithmetic is integer and every output is defined to the bit.
+ *
+ * order[n] lists indices into the batch's pictures (any order, repeats allowed).  Picture p has
+ * M = mb_width * mb_height cells; cell i, in raster order, is record mb_first + i.  Three optional
+ * tight tensors (a NULL pointer: not wanted); B = blocks per macroblock (6, 8 or 12):
+ *
+ * mv: int16 [n][8][mbh][mbw].  Channel c = 4 s + 2 r + k: s the direction (0 forward, 1 backward),
+ *     r the vector / destination field (0 top lines, 1 bottom lines), k = 0 for x, 1 for y.  Units
+ *     are FRAME half-pel luma units: the prediction of a destination sample is read at its
+ *     position plus the vector.  Direction s is used when the MB is not MP2VG_MB_INTRA and its
+ *     flag bit (FWD for s = 0, BWD for s = 1) is set, or s = 0 and neither bit is set (the
+ *     decode's own rule).
+ *         unused direction:       the four channels of s are 0, whatever the record's mv holds
+ *         used, frame MC:         both r carry mv[0][s][k]
+ *         used, MP2VG_MB_FIELD_MC: x = mv[r][s][0], y = 2 mv[r][s][1] + 2 (sel - r), sel = 1 when
+ *                                 MP2VG_MB_FS_BIT(r, s) is set, else 0
+ *     (the record's vertical component is in field half-pels, and destination lines r, r + 2, ...
+ *     read reference lines of parity sel: mv_y + sel - r frame lines).  Every value fits int16 for
+ *     f_code <= 9.
+ * info: uint16 [n][4][mbh][mbw]: flags & 0x0F1F (the five type bits and the four field selects),
+ *     cbp, qscale, ncoef.
+ * act: int32 [n][2][B][mbh][mbw], over the MB's words [coef_off, coef_off + ncoef), block b =
+ *     MP2VG_COEF_BLOCK: plane 0 the number of words of block b (DC and '1s' words included); plane
+ *     1 the sum of |level| (MP2VG_COEF_LEVEL, absolute value in 32 bits; a '1s' word counts 1) over
+ *     the words of block b without MP2VG_COEF_DC.  A word whose block index is >= B is ignored. */
+/* byte sizes of mv, info and act for n pictures (1 .. 65535) of the geometry; host only */
+int  mp2vg_motion_bytes(const mp2vg_config_t* cfg, int32_t n, uint64_t bytes[3]);
+/* The host twin: the same tensors from host records into host buffers, no device needed.  Rejects
+ * a record batch exactly as mp2vg_batch_validate does (over a pool of as many slots as the
+ * pictures name), then n and order as mp2vg_motion_batch; nothing is written on failure. */
+int  mp2vg_motion_records(const mp2vg_config_t* cfg, const mp2vg_picture_t* pics, int32_t npics,
+                          const mp2vg_mb_t* mbs, uint64_t nmbs, const uint32_t* coefs, uint64_t ncoefs,
+                          const int32_t* order, int32_t n, int16_t* mv, uint16_t* info, int32_t* act);
+/* The resident batch's tensors into device memory of the context's device: at least one of mv,
+ * info, act non-NULL, each 4-byte aligned, and bytes[t] of each given tensor equal to
+ * mp2vg_motion_bytes.  MP2VG_E_STATE when no batch is resident; MP2VG_E_INVALID for n <= 0,
+ * n > 65535, an index outside the batch's pictures, no output, a wrong size or alignment, with the
+ * reason in mp2vg_last_error() and nothing written.  Asynchronous like mp2vg_export_slots: one
+ * enqueue on the context's main stream behind the batch's upload (for mp2vg_batch_upload_es,
+ * behind its emit pass), complete after mp2vg_synchronize; needs no mp2vg_batch_decode and does
+ * not disturb one.  The upload that next reuses the batch's bank waits for it.  The order list is
+ * copied before the call returns; the main stream is not ordered with streams of the caller's
+ * (see mp2vg_export_slots). */
+int  mp2vg_motion_batch(mp2vg_ctx_t* ctx, const int32_t* order, int32_t n, void* mv, void* info, void* act,
+                        const uint64_t bytes[3]);
+/* diagnostics: device time (ms, HIP events on the main stream) of the kernels of the last
+ * mp2vg_motion_batch, the order list's copy excluded; waits for them.  MP2VG_E_STATE before the
+ * first one (tools/motion_bench.py). */
+int  mp2vg_last_motion_time(mp2vg_ctx_t* ctx, float* ms);
+
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c
  * (decoder.h:124-130), with the reference's field names (mp2v_hdr.h:61-141) and parsed the way

@@ -176,6 +176,7 @@ EXPORTS = [
     "mp2vg_scan_gop_index", "mp2vg_scan_shards", "mp2vg_scan_stream_headers", "mp2vg_scan_free",
     "mp2vg_scan_parse_host", "mp2vg_batch_upload_es", "mp2vg_batch_record_counts",
     "mp2vg_batch_download_records", "mp2vg_last_parse_times",
+    "mp2vg_motion_bytes", "mp2vg_motion_records", "mp2vg_motion_batch", "mp2vg_last_motion_time",
 ]
 
 _lib = None
@@ -275,6 +276,10 @@ def lib():
         "mp2vg_batch_record_counts": ([VP, P(U64), P(U64)], ctypes.c_int),
         "mp2vg_batch_download_records": ([VP, VP, U64, VP, U64], ctypes.c_int),
         "mp2vg_last_parse_times": ([VP, P(ctypes.c_float)], ctypes.c_int),
+        "mp2vg_motion_bytes": ([P(Config), I32, P(U64)], ctypes.c_int),
+        "mp2vg_motion_records": ([P(Config), VP, I32, VP, U64, VP, U64, P(I32), I32, VP, VP, VP], ctypes.c_int),
+        "mp2vg_motion_batch": ([VP, P(I32), I32, VP, VP, VP, P(U64)], ctypes.c_int),
+        "mp2vg_last_motion_time": ([VP, P(ctypes.c_float)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

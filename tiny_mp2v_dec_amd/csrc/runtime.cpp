@@ -18,6 +18,7 @@
 
 #include "export_kernel.h"
 #include "hipchk.h"
+#include "motion_kernel.h"
 #include "parse_kernel.h"
 #include "recon_kernel.h"
 #include "syntax.h"
@@ -205,6 +206,9 @@ struct mp2vg_ctx {
     // when the main stream was last synchronised.  Callers that never export never wait.
     std::vector<uint32_t> swaited;
     uint32_t export_synced = 0;
+    // mp2vg_motion_batch: start and end of the last one's kernels (mp2vg_last_motion_time)
+    hipEvent_t motion_ev[2] = {nullptr, nullptr};
+    bool motion_timed = false;
 
     // the device parse's own state (parse_dev.cpp: bitstream, tables, per-slice results, events),
     // created at the first mp2vg_batch_upload_es and freed by es_free at destroy
@@ -346,6 +350,8 @@ extern "C" int mp2vg_destroy(mp2vg_ctx_t* c) {
         if (e.done) hipEventDestroy(e.done);
     }
     if (c->export_ev) hipEventDestroy(c->export_ev);
+    for (auto e : c->motion_ev)
+        if (e) hipEventDestroy(e);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (auto st : c->sstreams) hipStreamSynchronize(st);
     for (auto e : c->sev) hipEventDestroy(e);
@@ -1585,6 +1591,18 @@ static int batch_decode(mp2vg_ctx_t* c) {
     return MP2VG_OK;
 }
 
+extern "C" int mp2vg_last_motion_time(mp2vg_ctx_t* c, float* ms) {
+    if (!c || !ms) return MP2VG_E_INVALID;
+    if (!c->motion_timed) {
+        set_error("no motion export enqueued");
+        return MP2VG_E_STATE;
+    }
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipEventSynchronize(c->motion_ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, c->motion_ev[0], c->motion_ev[1]));
+    return MP2VG_OK;
+}
+
 extern "C" int mp2vg_synchronize(mp2vg_ctx_t* c) {
     if (!c) return MP2VG_E_INVALID;
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -2292,5 +2310,48 @@ int export_enqueued(mp2vg_ctx* c) {
     HIPCHK(hipEventRecord(c->export_ev, c->stream));
     c->eseq++;
     return MP2VG_OK;
+}
+
+// What mp2vg_motion_batch (motion.cpp) needs from a context: the bank of the last upload instead
+// of the slot pool.  Its order list goes through the exports' staging ring.
+int motion_source(const mp2vg_ctx* c, MotionSource* s) {
+    if (!c->batch_ready) {
+        set_error("no batch uploaded");
+        return MP2VG_E_STATE;
+    }
+    const Bank& b = c->bank[c->cur];
+    s->device = c->cfg.device;
+    s->nb = c->g.nblocks;
+    s->mbw = c->cfg.width / 16, s->mbh = c->cfg.height / 16;
+    s->npics = b.npics;
+    s->d_pics = b.d_pics;
+    s->d_mbs = b.d_mbs;
+    s->d_coefs = b.d_coefs;
+    s->stream = c->stream;
+    return MP2VG_OK;
+}
+
+int motion_begin(mp2vg_ctx* c) {
+    // `uploaded` is recorded on the copy stream behind the record copies and, for a batch parsed
+    // on the device, behind the emit pass that runs on that stream
+    HIPCHK(hipStreamWaitEvent(c->stream, c->bank[c->cur].uploaded, 0));
+    c->motion_timed = false;
+    for (auto& e : c->motion_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(c->motion_ev[0], c->stream));
+    return MP2VG_OK;
+}
+
+int motion_enqueued(mp2vg_ctx* c) {
+    if (c->motion_ev[1] && hipEventRecord(c->motion_ev[1], c->stream) == hipSuccess) c->motion_timed = true;
+    // the bank first: whatever fails below, the upload that next reuses the bank must wait for the
+    // kernels already enqueued (were the record itself to fail, this call waits for the stream)
+    Bank& b = c->bank[c->cur];
+    const hipError_t ce = hipEventRecord(b.consumed, c->stream);
+    b.decoded = true;
+    const int rc = export_enqueued(c);
+    if (ce != hipSuccess) HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(ce);
+    return rc;
 }
 }  // namespace mp2vg

@@ -230,6 +230,7 @@ class DeviceContext:
         check(lib().mp2vg_create(ctypes.byref(self.cfg), ctypes.byref(self.h)), "create")
         self.pw, self.ph, self.stride, self.slot_bytes = _lib.geometry(width, height, chroma_format)
         self.nslots = slots
+        self.batch_pictures = 0  # pictures of the resident batch (export_motion's default order)
 
     def close(self):
         if self.h:
@@ -271,8 +272,10 @@ class DeviceContext:
         mbs = np.ascontiguousarray(mbs, MB_DTYPE)
         coefs = np.ascontiguousarray(coefs, np.uint32)
         vp = ctypes.c_void_p
+        self.batch_pictures = 0
         check(lib().mp2vg_batch_upload(self.h, pics.ctypes.data_as(vp), len(pics), mbs.ctypes.data_as(vp), len(mbs),
                                        coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs)), "batch_upload")
+        self.batch_pictures = len(pics)
 
     def upload_es(self, scan, first=0, npics=None, pics=None):
         """Pictures [first, first + npics) of a Scan as the resident batch, their slices parsed on
@@ -285,7 +288,9 @@ class DeviceContext:
             if len(pics) != npics:
                 raise ValueError("pics must hold one record per picture of the range")
             ptr = pics.ctypes.data_as(ctypes.c_void_p)
+        self.batch_pictures = 0
         check(lib().mp2vg_batch_upload_es(self.h, scan.h, ptr, int(first), int(npics)), "batch_upload_es")
+        self.batch_pictures = int(npics)
 
     def download_records(self):
         """(mbs, coefs) of the resident batch, copied from HBM (mp2vg_batch_download_records)."""
@@ -471,6 +476,38 @@ class DeviceContext:
             self.synchronize()
         return o
 
+    def export_motion(self, order=None, mv=True, info=True, act=True, sync=True):
+        """The resident batch's motion field and block activity as torch tensors on this context's
+        device (mp2vg_motion_batch, include/mp2vg.h "motion export"): (mv int16 (n, 8, mbh, mbw),
+        info uint16 (n, 4, mbh, mbw), act int32 (n, 2, B, mbh, mbw)), None for one not asked for.
+        order: indices into the batch's pictures, any order, repeats allowed (None: every picture
+        in batch order).  Reads the records, not the slots: no decode() is needed.  Stream ordering
+        and sync as export_rgb."""
+        import torch
+        if order is None:
+            order = np.arange(self.batch_pictures, dtype=np.int32)
+        order = np.ascontiguousarray(order, np.int32).ravel()
+        n, mbw, mbh = len(order), self.width // 16, self.height // 16
+        nb = {1: 6, 2: 8, 3: 12}[self.chroma_format]
+        dev = torch.device("cuda", self.cfg.device)
+        shapes = [((n, 8, mbh, mbw), torch.int16), ((n, 4, mbh, mbw), torch.uint16), ((n, 2, nb, mbh, mbw), torch.int32)]
+        outs = [torch.empty(s, dtype=d, device=dev) if want else None
+                for (s, d), want in zip(shapes, (mv, info, act))]
+        torch.cuda.synchronize(dev)  # the allocator's earlier users of these blocks have finished
+        bytes3 = (ctypes.c_uint64 * 3)(*[0 if t is None else t.numel() * t.element_size() for t in outs])
+        ptrs = [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in outs]
+        check(lib().mp2vg_motion_batch(self.h, order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, ptrs[0],
+                                       ptrs[1], ptrs[2], bytes3), "motion_batch")
+        if sync:
+            self.synchronize()
+        return tuple(outs)
+
+    def motion_time_ms(self):
+        """Device ms of the kernels of the last export_motion (mp2vg_last_motion_time)."""
+        ms = ctypes.c_float()
+        check(lib().mp2vg_last_motion_time(self.h, ctypes.byref(ms)), "last_motion_time")
+        return ms.value
+
     def digests(self, slots):
         slots = np.ascontiguousarray(slots, np.int32)
         out = np.zeros(len(slots), np.uint64)
@@ -634,6 +671,84 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
                               fields=None if modes is None else modes[i:i + len(part)], place=place, pad=pad)
         ctx.synchronize()
         return out
+
+
+def motion_bytes(width, height, chroma_format, n):
+    """(mv, info, act) byte sizes of n pictures (mp2vg_motion_bytes)."""
+    cfg = _lib.make_config(width, height, chroma_format)
+    b = (ctypes.c_uint64 * 3)()
+    check(lib().mp2vg_motion_bytes(ctypes.byref(cfg), int(n), b), "motion_bytes")
+    return tuple(int(v) for v in b)
+
+
+def motion_host(pics, mbs, coefs, width, height, chroma_format, order=None):
+    """numpy (mv, info, act) of host records through the host twin of the motion export
+    (mp2vg_motion_records; include/mp2vg.h "motion export"), no device: mv int16 (n, 8, mbh, mbw),
+    info uint16 (n, 4, mbh, mbw), act int32 (n, 2, B, mbh, mbw).  order: indices into pics (None:
+    every picture in batch order).  Raises Mp2vgError for a batch the upload would refuse."""
+    cfg = _lib.make_config(width, height, chroma_format)
+    pics = np.ascontiguousarray(pics, PIC_DTYPE)
+    mbs = np.ascontiguousarray(mbs, MB_DTYPE)
+    coefs = np.ascontiguousarray(coefs, np.uint32)
+    order = np.arange(len(pics), dtype=np.int32) if order is None else np.ascontiguousarray(order, np.int32).ravel()
+    n, mbw, mbh = len(order), width // 16, height // 16
+    nb = {1: 6, 2: 8, 3: 12}[chroma_format]
+    mv = np.zeros((n, 8, mbh, mbw), np.int16)
+    info = np.zeros((n, 4, mbh, mbw), np.uint16)
+    act = np.zeros((n, 2, nb, mbh, mbw), np.int32)
+    vp = ctypes.c_void_p
+    check(lib().mp2vg_motion_records(ctypes.byref(cfg), pics.ctypes.data_as(vp), len(pics), mbs.ctypes.data_as(vp),
+                                     len(mbs), coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs),
+                                     order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, mv.ctypes.data_as(vp),
+                                     info.ctypes.data_as(vp), act.ctypes.data_as(vp)), "motion_records")
+    return mv, info, act
+
+
+def reference_pictures(pics):
+    """int32 (n, 2): per picture of a batch, the batch index of its forward and of its backward
+    reference: the last earlier picture that wrote fwd_slot / bwd_slot, -1 if there is none."""
+    out = np.full((len(pics), 2), -1, np.int32)
+    writer = {}
+    for i, p in enumerate(pics):
+        for s, name in enumerate(("fwd_slot", "bwd_slot")):
+            out[i, s] = writer.get(int(p[name]), -1) if int(p[name]) >= 0 else -1
+        writer[int(p["dst_slot"])] = i
+    return out
+
+
+def reference_distances(pics, display):
+    """int32 (n, 2), in display order: the signed display-order distance from each picture to its
+    forward and backward reference (reference_pictures), 0 where there is none."""
+    display = np.asarray(display, np.int64)
+    pos = np.zeros(len(pics), np.int64)
+    pos[display] = np.arange(len(display))
+    ref = reference_pictures(pics)[display].astype(np.int64)
+    here = np.arange(len(display))[:, None]
+    return np.where(ref >= 0, pos[np.maximum(ref, 0)] - here, 0).astype(np.int32)
+
+
+def decode_motion(es, width, height, chroma_format, parse="device", device=0):
+    """The motion field and block activity of a whole elementary stream in display order, with no
+    reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
+    parse (parse="host": Parsed, upload) the stream, make it resident and export
+    (DeviceContext.export_motion).  A dict of mv, info and act (torch tensors on cuda:<device>) and
+    dist, numpy int32 (n, 2): the signed display-order distance from each picture to its forward
+    and backward reference, 0 where there is none (vectors per frame: mv / dist).  At most 65535
+    pictures."""
+    if parse not in ("device", "host"):
+        raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
+    import torch
+    torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
+    parsed = (Scan if parse == "device" else Parsed)(es, width, height, chroma_format)
+    if not parsed.npics:
+        raise ValueError("the stream has no pictures")
+    with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
+        if parse == "device":
+            ctx.upload_es(parsed)
+        else:
+            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        mv, info, act = ctx.export_motion(parsed.display)
+    return {"mv": mv, "info": info, "act": act, "dist": reference_distances(parsed.pics, parsed.display)}
 
 
 def frame_yuv_bytes(planes):
