@@ -624,6 +624,67 @@ int  mp2vg_motion_batch(mp2vg_ctx_t* ctx, const int32_t* order, int32_t n, void*
  * first one (tools/motion_bench.py). */
 int  mp2vg_last_motion_time(mp2vg_ctx_t* ctx, float* ms);
 
+/* ---- residual export ---------------------------------------------------------------------
+ * The coded prediction error as sample planes: what the stream codes for each block after
+ * dequantisation and the inverse transform and BEFORE it is added to the prediction, read from the
+ * resident record batch like the motion export (no decode, no slots), one kernel launch per call
+ * (residual.hip).  All arithmetic is integer and every output is defined to the bit.
+ *
+ * For picture p and macroblock m, block b (0 .. B - 1) is coded when bit b of cbp is set.  Its 64
+ * coefficients QFS are what the decode makes of the MB's words [coef_off, coef_off + ncoef) whose
+ * MP2VG_COEF_BLOCK is b, in any order (reference parse_block, mb_decoder.cpp:74-155): matrix
+ * W[(b < 6 ? 0 : 2) + (intra ? 0 : 1)], the MB's qscale, the picture's alternate_scan; a word with
+ * MP2VG_COEF_DC sets QFS[0] to its level and stays out of the mismatch sum; a FIRST1S word is
+ * (3 W[i] qs) >> 5 with the level's sign, unclamped; any other word is (|level| W[i] qs) >> 4
+ * (intra) or ((2 |level| + 1) W[i] qs) >> 5, signed, truncated to int16 and then clamped to
+ * -2048 .. 2047; position 63 has bit 0 toggled when the sum of the words' values is even.  A coded
+ * block without words is legal: all zeros with position 63 toggled to 1.  A word whose block is
+ * not coded, or is >= B, is ignored.
+ *     r[y][x] = idct(QFS)[y][x] >> 6
+ * is the int16 value the reference adds to the prediction (inverse_dct_template, idct_sse2.hpp:
+ * 96-120: both saturating 16-bit passes, then the arithmetic shift, before adds / packus).  The
+ * exported value is
+ *     MP2VG_RESIDUAL_I16: R = clamp(r, -255, 255)        MP2VG_RESIDUAL_I8: R = clamp(r, -128, 127)
+ * The int16 clamp loses nothing reconstruction can see: clip8(p + r) == clip8(p + clamp(r, -255,
+ * 255)) for every p in 0 .. 255.
+ * Placement is the decode's (mb_decoder.cpp:166-196): luma blocks 0-3 and chroma blocks 4 .. B - 1
+ * at their MB's position in planes of the CODED size; MP2VG_MB_DCT_FIELD interleaves the lines of
+ * luma, and of chroma where the format is not 4:2:0.  Every sample of a block that is not coded is
+ * 0 (skipped MBs have cbp = 0).  Intra MBs are exported like any other (clip8(R) is their decoded
+ * sample); with MP2VG_RESIDUAL_ZERO_INTRA they are written as zeros.  Records that repeat a scan
+ * position inside one block cannot come from a parser: the values of that block are unspecified,
+ * as the decode's are, and nothing outside the outputs is touched.
+ *
+ * order[n] as in the motion export (1 .. 65535 entries).  Three optional tight tensors of int16 or
+ * int8 elements (NULL: not wanted): y [n][H][W], cb and cr [n][ch][cw] at the chroma format's plane
+ * size; cb and cr are given together or not at all, and at least one of the three is given.  Every
+ * element of every given tensor is written exactly once (the zeros too); nothing is read back. */
+enum { MP2VG_RESIDUAL_I16 = 0, MP2VG_RESIDUAL_I8 = 1 };
+enum { MP2VG_RESIDUAL_ZERO_INTRA = 1 };
+/* byte sizes of y, cb and cr for n pictures (1 .. 65535) of the geometry; host only */
+int  mp2vg_residual_bytes(const mp2vg_config_t* cfg, int32_t n, int32_t dtype, uint64_t bytes[3]);
+/* The host twin: the same planes from host records into host buffers, no device needed.  Rejects a
+ * record batch exactly as mp2vg_motion_records does, then n, order, dtype, flags and the outputs
+ * as mp2vg_residual_batch (host buffers may have any alignment); nothing is written on failure. */
+int  mp2vg_residual_records(const mp2vg_config_t* cfg, const mp2vg_picture_t* pics, int32_t npics,
+                            const mp2vg_mb_t* mbs, uint64_t nmbs, const uint32_t* coefs, uint64_t ncoefs,
+                            const int32_t* order, int32_t n, int32_t dtype, int32_t flags, void* y, void* cb,
+                            void* cr);
+/* The resident batch's planes into device memory of the context's device: each given pointer
+ * 16-byte aligned and bytes[t] of each given tensor equal to mp2vg_residual_bytes.  MP2VG_E_STATE
+ * when no batch is resident; MP2VG_E_INVALID for a bad n, index, dtype, flag bit, size or
+ * alignment, no output, or cb without cr, with the reason in mp2vg_last_error() and nothing
+ * written.  Asynchronous and ordered exactly like mp2vg_motion_batch: one enqueue on the context's
+ * main stream behind the batch's upload (mp2vg_batch_upload or mp2vg_batch_upload_es), complete
+ * after mp2vg_synchronize; needs no mp2vg_batch_decode and does not disturb one; the upload that
+ * next reuses the bank waits for it.  The order list is copied before the call returns. */
+int  mp2vg_residual_batch(mp2vg_ctx_t* ctx, const int32_t* order, int32_t n, int32_t dtype, int32_t flags,
+                          void* y, void* cb, void* cr, const uint64_t bytes[3]);
+/* diagnostics: device time (ms, HIP events on the main stream) of the kernel of the last
+ * mp2vg_residual_batch, the order list's copy excluded; waits for it.  MP2VG_E_STATE before the
+ * first one (tools/residual_bench.py). */
+int  mp2vg_last_residual_time(mp2vg_ctx_t* ctx, float* ms);
+
 /* ---- stream headers ----------------------------------------------------------------------
  * The sequence-level headers the reference keeps as public members of mp2v_decoder_c
  * (decoder.h:124-130), with the reference's field names (mp2v_hdr.h:61-141) and parsed the way

@@ -4,8 +4,9 @@ Host record emitter + HIP/CDNA4 kernels behind the C ABI of include/mp2vg.h, wit
 reference's decoder API (mp2v_decoder_c / frame_c / decoder_config_t) mirrored in decoder.py.
 """
 from ._lib import MB_DTYPE, PIC_DTYPE, Mp2vgError, lib  # noqa: F401
-from .records import (DeviceContext, Parsed, decode_motion, decode_rgb, decode_tensor, generate_es,  # noqa: F401
-                      motion_host, reference_pictures)
+from .records import (DeviceContext, Parsed, decode_motion, decode_residual, decode_rgb, decode_tensor,  # noqa: F401
+                      generate_es, motion_host, reference_pictures, residual_bytes, residual_host)
 
-__all__ = ["DeviceContext", "Parsed", "decode_motion", "decode_rgb", "decode_tensor", "generate_es", "motion_host",
-           "reference_pictures", "MB_DTYPE", "PIC_DTYPE", "Mp2vgError", "lib"]
+__all__ = ["DeviceContext", "Parsed", "decode_motion", "decode_residual", "decode_rgb", "decode_tensor", "generate_es",
+           "motion_host", "reference_pictures", "residual_bytes", "residual_host", "MB_DTYPE", "PIC_DTYPE",
+           "Mp2vgError", "lib"]

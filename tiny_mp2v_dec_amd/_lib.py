@@ -177,6 +177,7 @@ EXPORTS = [
     "mp2vg_scan_parse_host", "mp2vg_batch_upload_es", "mp2vg_batch_record_counts",
     "mp2vg_batch_download_records", "mp2vg_last_parse_times",
     "mp2vg_motion_bytes", "mp2vg_motion_records", "mp2vg_motion_batch", "mp2vg_last_motion_time",
+    "mp2vg_residual_bytes", "mp2vg_residual_records", "mp2vg_residual_batch", "mp2vg_last_residual_time",
 ]
 
 _lib = None
@@ -280,6 +281,11 @@ def lib():
         "mp2vg_motion_records": ([P(Config), VP, I32, VP, U64, VP, U64, P(I32), I32, VP, VP, VP], ctypes.c_int),
         "mp2vg_motion_batch": ([VP, P(I32), I32, VP, VP, VP, P(U64)], ctypes.c_int),
         "mp2vg_last_motion_time": ([VP, P(ctypes.c_float)], ctypes.c_int),
+        "mp2vg_residual_bytes": ([P(Config), I32, I32, P(U64)], ctypes.c_int),
+        "mp2vg_residual_records": ([P(Config), VP, I32, VP, U64, VP, U64, P(I32), I32, I32, I32, VP, VP, VP],
+                                   ctypes.c_int),
+        "mp2vg_residual_batch": ([VP, P(I32), I32, I32, I32, VP, VP, VP, P(U64)], ctypes.c_int),
+        "mp2vg_last_residual_time": ([VP, P(ctypes.c_float)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -298,6 +304,23 @@ def check(status, what):
 
 MP2VG_DECODER_DEVICE_FRAMES, MP2VG_CTX_ONE_STREAM = 1, 2  # mp2vg_config_t.reserved flags
 MP2VG_DECODER_DEVICE_PARSE = 4  # drop-in decoder: slices parsed on the device (mp2vg_batch_upload_es)
+RESIDUAL_DTYPES = {"int16": 0, "int8": 1}  # MP2VG_RESIDUAL_I16 / I8
+RESIDUAL_ZERO_INTRA = 1
+
+
+def residual_dtype(dtype):
+    """MP2VG_RESIDUAL_* code of 'int16' / 'int8' (or of a numpy / torch dtype of that name)."""
+    name = str(dtype).replace("torch.", "")
+    if name not in RESIDUAL_DTYPES:
+        raise ValueError(f"residual dtype {dtype!r}: expected 'int16' or 'int8'")
+    return name, RESIDUAL_DTYPES[name]
+
+
+def residual_shapes(width, height, chroma_format, n):
+    """Shapes of the y, cb and cr planes of n pictures."""
+    cw = width if chroma_format == 3 else width // 2
+    ch = height // 2 if chroma_format == 1 else height
+    return (n, height, width), (n, ch, cw), (n, ch, cw)
 
 
 def make_config(width, height, chroma_format, pool=10, threads=0, reordering=True, device=0, flags=0):

@@ -19,6 +19,7 @@
 #include "export_kernel.h"
 #include "hipchk.h"
 #include "motion_kernel.h"
+#include "residual_kernel.h"
 #include "parse_kernel.h"
 #include "recon_kernel.h"
 #include "syntax.h"
@@ -209,6 +210,9 @@ struct mp2vg_ctx {
     // mp2vg_motion_batch: start and end of the last one's kernels (mp2vg_last_motion_time)
     hipEvent_t motion_ev[2] = {nullptr, nullptr};
     bool motion_timed = false;
+    // mp2vg_residual_batch: the same pair for its kernel (mp2vg_last_residual_time)
+    hipEvent_t residual_ev[2] = {nullptr, nullptr};
+    bool residual_timed = false;
 
     // the device parse's own state (parse_dev.cpp: bitstream, tables, per-slice results, events),
     // created at the first mp2vg_batch_upload_es and freed by es_free at destroy
@@ -351,6 +355,8 @@ extern "C" int mp2vg_destroy(mp2vg_ctx_t* c) {
     }
     if (c->export_ev) hipEventDestroy(c->export_ev);
     for (auto e : c->motion_ev)
+        if (e) hipEventDestroy(e);
+    for (auto e : c->residual_ev)
         if (e) hipEventDestroy(e);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (auto st : c->sstreams) hipStreamSynchronize(st);
@@ -1603,6 +1609,18 @@ extern "C" int mp2vg_last_motion_time(mp2vg_ctx_t* c, float* ms) {
     return MP2VG_OK;
 }
 
+extern "C" int mp2vg_last_residual_time(mp2vg_ctx_t* c, float* ms) {
+    if (!c || !ms) return MP2VG_E_INVALID;
+    if (!c->residual_timed) {
+        set_error("no residual export enqueued");
+        return MP2VG_E_STATE;
+    }
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipEventSynchronize(c->residual_ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, c->residual_ev[0], c->residual_ev[1]));
+    return MP2VG_OK;
+}
+
 extern "C" int mp2vg_synchronize(mp2vg_ctx_t* c) {
     if (!c) return MP2VG_E_INVALID;
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -2342,10 +2360,10 @@ int motion_begin(mp2vg_ctx* c) {
     return MP2VG_OK;
 }
 
-int motion_enqueued(mp2vg_ctx* c) {
-    if (c->motion_ev[1] && hipEventRecord(c->motion_ev[1], c->stream) == hipSuccess) c->motion_timed = true;
-    // the bank first: whatever fails below, the upload that next reuses the bank must wait for the
-    // kernels already enqueued (were the record itself to fail, this call waits for the stream)
+// after a kernel that read the bank: the bank first -- whatever fails below, the upload that next
+// reuses the bank must wait for the kernels already enqueued (were the record itself to fail, this
+// call waits for the stream)
+static int bank_read_enqueued(mp2vg_ctx* c) {
     Bank& b = c->bank[c->cur];
     const hipError_t ce = hipEventRecord(b.consumed, c->stream);
     b.decoded = true;
@@ -2353,5 +2371,26 @@ int motion_enqueued(mp2vg_ctx* c) {
     if (ce != hipSuccess) HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(ce);
     return rc;
+}
+
+int motion_enqueued(mp2vg_ctx* c) {
+    if (c->motion_ev[1] && hipEventRecord(c->motion_ev[1], c->stream) == hipSuccess) c->motion_timed = true;
+    return bank_read_enqueued(c);
+}
+
+// The residual export (residual.cpp) reads the same bank (motion_source) under the same ordering,
+// with a pair of timing events of its own.
+int residual_begin(mp2vg_ctx* c) {
+    HIPCHK(hipStreamWaitEvent(c->stream, c->bank[c->cur].uploaded, 0));
+    c->residual_timed = false;
+    for (auto& e : c->residual_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(c->residual_ev[0], c->stream));
+    return MP2VG_OK;
+}
+
+int residual_enqueued(mp2vg_ctx* c) {
+    if (c->residual_ev[1] && hipEventRecord(c->residual_ev[1], c->stream) == hipSuccess) c->residual_timed = true;
+    return bank_read_enqueued(c);
 }
 }  // namespace mp2vg

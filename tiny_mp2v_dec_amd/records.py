@@ -508,6 +508,38 @@ class DeviceContext:
         check(lib().mp2vg_last_motion_time(self.h, ctypes.byref(ms)), "last_motion_time")
         return ms.value
 
+    def export_residual(self, order=None, dtype="int16", chroma=True, zero_intra=False, sync=True):
+        """The resident batch's coded prediction error as torch tensors on this context's device
+        (mp2vg_residual_batch, include/mp2vg.h "residual export"): (y (n, H, W), cb, cr (n, ch, cw))
+        of int16 (clamped to -255 .. 255) or int8 (-128 .. 127); cb and cr are None without chroma.
+        order: indices into the batch's pictures, any order, repeats allowed (None: every picture
+        in batch order).  zero_intra: intra macroblocks are written as zeros.  Reads the records,
+        not the slots: no decode() is needed.  Stream ordering and sync as export_rgb."""
+        import torch
+        name, code = _lib.residual_dtype(dtype)
+        if order is None:
+            order = np.arange(self.batch_pictures, dtype=np.int32)
+        order = np.ascontiguousarray(order, np.int32).ravel()
+        dev = torch.device("cuda", self.cfg.device)
+        shapes = _lib.residual_shapes(self.width, self.height, self.chroma_format, len(order))
+        outs = [torch.empty(s, dtype=getattr(torch, name), device=dev) if want else None
+                for s, want in zip(shapes, (True, chroma, chroma))]
+        torch.cuda.synchronize(dev)  # the allocator's earlier users of these blocks have finished
+        bytes3 = (ctypes.c_uint64 * 3)(*[0 if t is None else t.numel() * t.element_size() for t in outs])
+        ptrs = [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in outs]
+        check(lib().mp2vg_residual_batch(self.h, order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(order), code,
+                                         _lib.RESIDUAL_ZERO_INTRA if zero_intra else 0, ptrs[0], ptrs[1], ptrs[2],
+                                         bytes3), "residual_batch")
+        if sync:
+            self.synchronize()
+        return tuple(outs)
+
+    def residual_time_ms(self):
+        """Device ms of the kernel of the last export_residual (mp2vg_last_residual_time)."""
+        ms = ctypes.c_float()
+        check(lib().mp2vg_last_residual_time(self.h, ctypes.byref(ms)), "last_residual_time")
+        return ms.value
+
     def digests(self, slots):
         slots = np.ascontiguousarray(slots, np.int32)
         out = np.zeros(len(slots), np.uint64)
@@ -749,6 +781,64 @@ def decode_motion(es, width, height, chroma_format, parse="device", device=0):
             ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
         mv, info, act = ctx.export_motion(parsed.display)
     return {"mv": mv, "info": info, "act": act, "dist": reference_distances(parsed.pics, parsed.display)}
+
+
+def residual_bytes(width, height, chroma_format, n, dtype="int16"):
+    """(y, cb, cr) byte sizes of n pictures (mp2vg_residual_bytes)."""
+    cfg = _lib.make_config(width, height, chroma_format)
+    b = (ctypes.c_uint64 * 3)()
+    check(lib().mp2vg_residual_bytes(ctypes.byref(cfg), int(n), _lib.residual_dtype(dtype)[1], b), "residual_bytes")
+    return tuple(int(v) for v in b)
+
+
+def residual_host(pics, mbs, coefs, width, height, chroma_format, order=None, dtype="int16", zero_intra=False):
+    """numpy (y, cb, cr) of host records through the host twin of the residual export
+    (mp2vg_residual_records; include/mp2vg.h "residual export"), no device: y (n, H, W), cb and cr
+    (n, ch, cw) of int16 or int8.  order: indices into pics (None: every picture in batch order).
+    Raises Mp2vgError for a batch the upload would refuse."""
+    name, code = _lib.residual_dtype(dtype)
+    cfg = _lib.make_config(width, height, chroma_format)
+    pics = np.ascontiguousarray(pics, PIC_DTYPE)
+    mbs = np.ascontiguousarray(mbs, MB_DTYPE)
+    coefs = np.ascontiguousarray(coefs, np.uint32)
+    order = np.arange(len(pics), dtype=np.int32) if order is None else np.ascontiguousarray(order, np.int32).ravel()
+    outs = [np.zeros(s, name) for s in _lib.residual_shapes(width, height, chroma_format, len(order))]
+    vp = ctypes.c_void_p
+    check(lib().mp2vg_residual_records(ctypes.byref(cfg), pics.ctypes.data_as(vp), len(pics), mbs.ctypes.data_as(vp),
+                                       len(mbs), coefs.ctypes.data_as(vp) if len(coefs) else None, len(coefs),
+                                       order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(order), code,
+                                       _lib.RESIDUAL_ZERO_INTRA if zero_intra else 0, outs[0].ctypes.data_as(vp),
+                                       outs[1].ctypes.data_as(vp), outs[2].ctypes.data_as(vp)), "residual_records")
+    return tuple(outs)
+
+
+def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int16", chroma=True, zero_intra=False,
+                    parse="device", device=0):
+    """The coded prediction error of an elementary stream's pictures in display order, with no
+    reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
+    parse (parse="host": Parsed, upload) the stream, make it resident and export once
+    (DeviceContext.export_residual).  pictures: display indices (None: all of them).  A dict of y, cb
+    and cr (torch tensors on cuda:<device>, cb and cr None without chroma) and types, numpy int32:
+    the picture_coding_type (1 I, 2 P, 3 B) of each exported picture.  Size: a 4:2:0 picture at
+    int16 is 2 x 1.5 x W x H bytes (half that at int8), so a long stream is exported in ranges of
+    pictures.  At most 65535 pictures."""
+    if parse not in ("device", "host"):
+        raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
+    import torch
+    torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
+    parsed = (Scan if parse == "device" else Parsed)(es, width, height, chroma_format)
+    if not parsed.npics:
+        raise ValueError("the stream has no pictures")
+    display = np.asarray(parsed.display, np.int32)
+    order = display if pictures is None else display[np.asarray(pictures, np.int64)]
+    with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
+        if parse == "device":
+            ctx.upload_es(parsed)
+        else:
+            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        y, cb, cr = ctx.export_residual(order, dtype=dtype, chroma=chroma, zero_intra=zero_intra)
+    types = np.asarray(parsed.pics["picture_coding_type"], np.int32)[order]
+    return {"y": y, "cb": cb, "cr": cr, "types": types}
 
 
 def frame_yuv_bytes(planes):
