@@ -114,8 +114,17 @@ typedef struct mp2vg_picture {
 } mp2vg_picture_t;                /* 288 bytes */
 
 /* ---- device context ------------------------------------------------------------------- */
+/* The largest width and height a config may hold.  Every entry point that takes a config refuses
+ * a larger one with MP2VG_E_INVALID (mp2vg_frame_geometry is the gate).  Three things meet at this
+ * size: MPEG-2 codes horizontal_size and vertical_size in 12 + 2 bits, so 16383, coded as 16384,
+ * is the largest picture a stream can describe; the records' int16 half-pel vectors can just span
+ * it (2 * (16384 - 16) = 32736); and the kernels address a slot and its anchor tiles with 32-bit
+ * offsets, the largest of which (a 4:4:4 slot's Cr tile plane, 2^30 + 2^29) stays below 2^31. */
+#define MP2VG_MAX_DIMENSION 16384
+
 typedef struct mp2vg_config {
-    int32_t width, height;       /* CODED size (multiples of 16), as the reference's config  */
+    int32_t width, height;       /* CODED size: multiples of 16, 16 .. MP2VG_MAX_DIMENSION, as
+                                    the reference's config                                    */
     int32_t chroma_format;       /* 1 = 4:2:0, 2 = 4:2:2, 3 = 4:4:4                          */
     int32_t pictures_pool_size;  /* number of device frame slots                             */
     int32_t num_threads;         /* host parse threads (0 = auto)                            */
@@ -748,7 +757,11 @@ typedef struct mp2vg_parsed mp2vg_parsed_t;
 
 /* Parse a whole elementary stream into records.  Pictures are numbered in decode order and
  * slot ids are decode indices (dst_slot = i; refs point at earlier indices).  Validates the
- * reference's input contract and returns MP2VG_E_UNSUPPORTED outside it. */
+ * reference's input contract and returns MP2VG_E_UNSUPPORTED outside it.  Part of
+ * that contract: the reference reads slice_vertical_position_extension when the 12-bit
+ * vertical_size_value is above 2800, so a stream whose vertical_size (14 bits) is above 2800 while
+ * its low 12 bits are not (4112 lines) is refused, with a reason that names vertical_size; 16384
+ * coded lines decode as vertical_size 16383.  cfg holds the coded size (MP2VG_MAX_DIMENSION). */
 int  mp2vg_parse_es(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cfg,
                     mp2vg_parsed_t** out);
 int  mp2vg_parsed_counts(const mp2vg_parsed_t* p, int32_t* npics, uint64_t* nmbs,

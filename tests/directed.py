@@ -3,7 +3,9 @@ enumerates the tap's address / phase space and its edge contacts, and batches wh
 carry exact coefficient-word counts.  Everything is deterministic from a seed; the coverage a
 batch achieves is recomputed from its finished records (sweep_coverage, group_totals), never taken
 from the way the records were chosen.  tests/test_directed_cpu.py asserts the coverage,
-tests/test_gpu_directed.py decodes the batches against the oracle."""
+tests/test_gpu_directed.py decodes the batches against the oracle.  The same builders at the
+geometry limits (16384 wide or high), the vertical long-vector batch, the tap sweep at the far
+corner and the sparse 16384 x 16384 frame are decoded by tests/test_gpu_limits.py."""
 import numpy as np
 
 from test_gpu_parity import _P, _inside  # noqa: F401  (_P re-exported for the directed tests)
@@ -143,9 +145,11 @@ class _Builder:
         return p
 
     def half_pel_vector(self):
-        """A small vector with both components odd that keeps this MB's reads inside."""
+        """A small vector with both components odd that keeps this MB's reads inside (in a picture
+        one MB wide or high, where no odd component is legal on that axis, that component is 0)."""
         x, y = self.pos()
-        c = [(a, b) for a in (-3, -1, 1, 3) for b in (-3, -1, 1, 3)
+        odd = (-3, -1, 1, 3)
+        c = [(a, b) for a in (odd if self.mbw > 1 else (0,)) for b in (odd if self.mbh > 1 else (0,))
              if _inside(self.width, self.height, self.cf, x, y, a, b, False, 0)]
         return c[int(self.rng.integers(len(c)))]
 
@@ -155,6 +159,32 @@ class _Builder:
             mv = np.zeros((2, 2, 2), np.int16)
             mv[0, 0] = self.half_pel_vector()
             self.mb(MB_FWD, self.textured_blocks(False), 2, mv)
+        return p
+
+    def textured_picture_np(self, ptype, fwd=-1):
+        """textured_i_picture (ptype 1) or textured_p_picture (ptype 2) for pictures of thousands of
+        MBs: the same recipe with the words of every block drawn at once in numpy (other random
+        numbers than the per-MB builders draw)."""
+        p = self.picture(ptype, fwd)
+        n, nb, intra, rng = self.mbw * self.mbh, self.nb, ptype == 1, self.rng
+        pos = np.sort(np.argsort(rng.random((n, nb, 63)), axis=2)[:, :, :12] + 1, axis=2)  # distinct, 1..63
+        lvl = rng.integers(1, 9, (n, nb, 12)) * rng.choice([-1, 1], (n, nb, 12))
+        col = ((np.arange(n) % self.mbw) & 7) << 26  # coef_pack's column bits
+        blk = np.arange(nb) << 22
+        words = (lvl & 0xFFFF) | pos << 16 | blk[None, :, None] | col[:, None, None]
+        if intra:
+            dc = rng.integers(480, 1568, (n, nb)) | blk[None, :] | col[:, None] | COEF_DC
+            words = np.concatenate([dc[:, :, None], words], axis=2)
+        per, off = words.shape[1] * words.shape[2], len(self.coefs)
+        self.coefs.extend(words.reshape(-1).tolist())
+        for k in range(n):
+            x, y = self.pos()
+            mv = None
+            if not intra:
+                mv = np.zeros((2, 2, 2), np.int16)
+                mv[0, 0] = self.half_pel_vector()
+            self.mbs.append((x, y, MB_INTRA if intra else MB_FWD, (1 << nb) - 1, 2, per, off + k * per, mv))
+            self.k += 1
         return p
 
     def small_residual(self):
@@ -419,9 +449,10 @@ def mb_taps(pics, mbs, p, i):
     return out
 
 
-def sweep_coverage(width, height, cf, pics, mbs):
+def sweep_coverage(width, height, cf, pics, mbs, window=None):
     """Per coverage key, from the records alone: the (mvx mod 32, mvy & 1) and (mvy mod 32,
-    mvx & 1) pairs, the signs of each component, the vectors, and the edge contacts per plane."""
+    mvx & 1) pairs, the signs of each component, the vectors, and the edge contacts per plane.
+    window = (first MB column, first MB row): only the MBs from there to the far corner count."""
     cov = {k: dict(xphase=set(), yphase=set(), sx=set(), sy=set(), vecs=set(), contacts=set(),
                    corners=set()) for k in KEYS}
     mbw, mbh = width // 16, height // 16
@@ -429,6 +460,8 @@ def sweep_coverage(width, height, cf, pics, mbs):
         first = int(pics[p]["mb_first"])
         for i in range(first, first + mbw * mbh):
             x, y = int(mbs["x"][i]), int(mbs["y"][i])
+            if window is not None and (x < window[0] or y < window[1]):
+                continue
             for key, r, s, vx, vy, field, fs in mb_taps(pics, mbs, p, i):
                 c = cov[key]
                 c["xphase"].add((vx % 32, vy & 1))
@@ -610,8 +643,12 @@ def long_vector_batch(width, height, cf, seed=909):
                 mv[r, s] = (vx, vy)
         return mv
 
-    B.textured_i_picture()
-    B.textured_p_picture(0)
+    if mbw * mbh > 1024:  # (the per-MB anchors take seconds there)
+        B.textured_picture_np(1)
+        B.textured_picture_np(2, 0)
+    else:
+        B.textured_i_picture()
+        B.textured_p_picture(0)
     for ptype in (2, 3):
         B.picture(ptype, 0, 1 if ptype == 3 else -1)
         for k in range(mbw * mbh):
@@ -622,3 +659,242 @@ def long_vector_batch(width, height, cf, seed=909):
                                                 MB_FWD | MB_BWD, MB_BWD)[k % 6]
             B.mb(flags, B.small_residual() if k % 4 == 3 else {}, 2, vectors(x, y, field, flags))
     return B.finish()
+
+
+def long_vertical_far(height, field):
+    """The longest legal vertical vector with half-pel: from MB row 0 to the last MB row, in frame
+    half-pels (frame MC) or field half-pels (field MC)."""
+    return (2 if not field else 1) * (height - 16) - 1
+
+
+_vertical = {}
+
+
+def long_vertical_batch(width, height, cf, seed=919):
+    """The vertical twin of long_vector_batch, on a narrow and tall picture: textured I and P
+    anchors (pictures 0 and 1), then a P picture from picture 0, a forward-only B picture from
+    picture 0, a backward-only B picture from picture 1 (both through the P loop) and a
+    two-direction B picture whose MBs are bidirectional, forward-only and backward-only in turn.
+    The first vector of an MB in row y steps from +long_vertical_far in row 0 to the negative of
+    that in the last row; the other direction of a bidirectional MB is the longest vector of its
+    row, to row 0 and to the last row (with half-pel) in turn.  MBs alternate between frame MC and
+    field MC like a chessboard, the field MBs running through all four (r0, r1) field selects per
+    direction every eight rows.  Every fourth MB carries a small residual."""
+    ck = (width, height, cf, seed)
+    if ck in _vertical:
+        return _vertical[ck]
+    B = _Builder(width, height, cf, seed + cf)
+    mbw, mbh = B.mbw, B.mbh
+    assert mbh > 48 and mbw > 1
+
+    def towards_zero(v, ok):
+        """v, or the nearest vector towards zero that keeps the reads inside."""
+        while v and not ok(v):
+            v -= 1 if v > 0 else -1
+        return v
+
+    def vectors(x, y, field, flags):
+        far = long_vertical_far(height, field)
+        unit = 1 if field else 2
+        mv = np.zeros((2, 2, 2), np.int16)
+        for r in range(2 if field else 1):
+            for s in range(2):
+                first = s == 0 if flags & MB_FWD else s == 1  # the direction that carries the stepped vector
+                if first:
+                    vy = far - (2 * far * y + (mbh - 1) // 2) // (mbh - 1)
+                else:
+                    vy = -16 * unit * y if (x + y // 2) % 2 == 0 else unit * (height - 16 - 16 * y) - 1
+                fs = (flags >> (8 + 2 * r + s)) & 1
+                vy = towards_zero(vy, lambda v: _inside(width, height, cf, x, y, 0, v, field, fs))
+                vx = _first_legal([(3, 1, -1, -3)[(y + r + s + j) % 4] for j in range(4)] + [0],
+                                  lambda v: _inside(width, height, cf, x, y, v, 0, field, fs))
+                assert _inside(width, height, cf, x, y, vx, vy, field, fs), (x, y, vx, vy)
+                mv[r, s] = (vx, vy)
+        return mv
+
+    B.textured_picture_np(1)
+    B.textured_picture_np(2, 0)
+    for ptype, fwd, bwd, kinds in ((2, 0, -1, (MB_FWD,)), (3, 0, -1, (MB_FWD,)), (3, -1, 1, (MB_BWD,)),
+                                   (3, 0, 1, (MB_FWD | MB_BWD, MB_FWD, MB_BWD))):
+        B.picture(ptype, fwd, bwd)
+        for k in range(mbw * mbh):
+            x, y = B.pos()
+            field = (x + y) % 2 == 1
+            flags = kinds[(x + y // 2) % len(kinds)]
+            if field:  # field selects (r0, r1): forward combination y // 2 mod 4, backward the next one
+                a, b = (y // 2) % 4, (y // 2 + 1) % 4
+                flags |= MB_FIELD_MC
+                flags |= (mb_fs_bit(0, 0) if a & 1 else 0) | (mb_fs_bit(1, 0) if a & 2 else 0)
+                flags |= (mb_fs_bit(0, 1) if b & 1 else 0) | (mb_fs_bit(1, 1) if b & 2 else 0)
+            B.mb(flags, B.small_residual() if k % 4 == 3 else {}, 2, vectors(x, y, field, flags))
+    _vertical[ck] = B.finish()
+    return _vertical[ck]
+
+
+def long_vertical_coverage(width, height, pics, mbs):
+    """Per coverage key, from the records alone: (the largest mvy, the smallest mvy) over the MBs
+    that apply a vector of that key; keys that no MB holds are missing."""
+    mbw, mbh = width // 16, height // 16
+    out = {}
+    for p in range(len(pics)):
+        first = int(pics[p]["mb_first"])
+        for i in range(first, first + mbw * mbh):
+            for key, r, s, vx, vy, field, fs in mb_taps(pics, mbs, p, i):
+                hi, lo = out.get(key, (vy, vy))
+                out[key] = (max(hi, vy), min(lo, vy))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# a frame of zero-vector MBs with a few hundred directed ones
+# ---------------------------------------------------------------------------------------------
+def sparse_frame_batch(width, height, cf, seed=16384):
+    """Records of a P picture (slot 2, forward slot 0) and a two-direction B picture (slot 3,
+    forward slot 0, backward slot 1), built in numpy for frames of a million MBs: every MB
+    predicts with the zero vector and no residual, except the directed ones -- the 8 x 8 MBs of
+    each corner and every fourth MB of the last MB row (the last luma tile bands).  A directed MB
+    draws its vectors over the whole legal range (its taps land anywhere in the reference, the end
+    of the last plane included), frame or field MC, P: forward, B: bidirectional, forward or
+    backward, with a small residual on every second one; MB (0, 0) and the last MB take the longest
+    vector towards the opposite corner.  Returns (pics, mbs, coefs, the directed MBs' record
+    indices per picture)."""
+    mbw, mbh, nb = width // 16, height // 16, NB[cf]
+    assert mbw >= 20 and mbh >= 16
+    n = mbw * mbh
+    rng = np.random.default_rng(seed)
+    pics = np.zeros(2, R.PIC_DTYPE)
+    pics["dst_slot"], pics["fwd_slot"], pics["bwd_slot"] = [2, 3], [0, 0], [-1, 1]
+    pics["picture_coding_type"], pics["mb_first"] = [2, 3], [0, n]
+    pics["mb_width"], pics["mb_height"], pics["W"] = mbw, mbh, 16
+    mbs = np.zeros(2 * n, R.MB_DTYPE)
+    mbs["x"], mbs["y"] = np.tile(np.arange(mbw), 2 * mbh), np.tile(np.repeat(np.arange(mbh), mbw), 2)
+    mbs["flags"][:n], mbs["flags"][n:], mbs["qscale"] = MB_FWD, MB_FWD | MB_BWD, 2
+    ex, ey = list(range(8)) + list(range(mbw - 8, mbw)), list(range(8)) + list(range(mbh - 8, mbh))
+    where = [(x, y) for y in ey for x in ex] + [(x, mbh - 1) for x in range(10, mbw - 8, 4)]
+    where.sort(key=lambda xy: (xy[1], xy[0]))  # raster order: the words follow their MBs
+    coefs, ncoef, directed = [], np.zeros(2 * n, np.int64), []
+    for p in range(2):
+        directed.append(np.array([p * n + y * mbw + x for x, y in where]))
+        for j, (x, y) in enumerate(where):
+            i = p * n + y * mbw + x
+            field = bool(rng.integers(0, 3) == 0) and (x, y) not in ((0, 0), (mbw - 1, mbh - 1))
+            flags = MB_FWD if p == 0 else (MB_FWD | MB_BWD, MB_FWD, MB_BWD)[j % 3]
+            if field:
+                flags |= MB_FIELD_MC | int(rng.integers(0, 16)) << 8
+            vs = 1 if field else 2
+            for r in range(2 if field else 1):
+                for s in range(2):
+                    fs = 1 if flags & mb_fs_bit(r, s) else 0
+                    vx = int(rng.integers(-32 * x, 2 * (width - 16 - 16 * x) + 1))
+                    vy = int(rng.integers(-16 * vs * y, vs * (height - 16 - 16 * y) + 1))
+                    if (x, y) == (0, 0):
+                        vx, vy = 2 * (width - 16) - 1, vs * (height - 16) - 1
+                    if (x, y) == (mbw - 1, mbh - 1):
+                        vx, vy = -2 * (width - 16), -vs * (height - 16)
+                    assert _inside(width, height, cf, x, y, vx, vy, field, fs), (x, y, vx, vy, field, fs)
+                    mbs["mv"][i, r, s] = (vx, vy)
+            mbs["flags"][i] = flags
+            if j % 2:
+                cbp = 0
+                for b in sorted(rng.choice(nb, 4, replace=False).tolist()):
+                    cbp |= 1 << b
+                    for pos in sorted(rng.choice(64, 3, replace=False).tolist()):
+                        coefs.append(coef_pack(int(rng.choice([-3, -2, -1, 1, 2, 3])), int(pos), b, 0, x))
+                        ncoef[i] += 1
+                mbs["cbp"][i] = cbp
+    mbs["ncoef"] = ncoef
+    mbs["coef_off"] = np.cumsum(ncoef) - ncoef
+    return pics, mbs, np.array(coefs, np.uint32), directed
+
+
+def textured_bytes(rng, n):
+    """n full-range bytes: 8 MiB + 13 seeded bytes, repeated (seconds faster than n random bytes
+    for a slot of 768 MiB; the period is no multiple of any row, tile or plane size)."""
+    return np.resize(np.frombuffer(rng.bytes(min(n, (8 << 20) + 13)), np.uint8), n)
+
+
+def sparse_frame_expected(exp, pics, mbs, coefs, directed):
+    """Slots 2 and 3 of exp (a helpers.SlotOracle whose slots 0 and 1 hold the references) after
+    sparse_frame_batch.  The zero-vector MBs come from their definition, whole slots at a time:
+    the forward reference's bytes in the P picture, (forward + backward + 1) >> 1 in the B picture
+    (as a | b - ((a ^ b) >> 1), which stays in uint8).  The directed MBs are then decoded by the
+    oracle, as pictures that hold those MB records alone (the oracle places an MB by its x and y)."""
+    sb = int(exp.g.slot_bytes)
+    a, b = exp.pool[:sb], exp.pool[sb:2 * sb]
+    exp.pool[2 * sb:3 * sb] = a
+    avg = exp.pool[3 * sb:4 * sb]
+    np.bitwise_or(a, b, out=avg)
+    avg -= (a ^ b) >> 1
+    sub = pics.copy()
+    sub["mb_first"] = [0, len(directed[0])]
+    sub["mb_width"], sub["mb_height"] = len(directed[0]), 1
+    exp.decode(sub, np.concatenate([mbs[directed[0]], mbs[directed[1]]]), coefs)
+
+
+# ---------------------------------------------------------------------------------------------
+# the tap sweep at the far corner of a large picture
+# ---------------------------------------------------------------------------------------------
+_corner = {}
+
+
+def corner_sweep(width, height, cf, sw, sh):
+    """mc_sweep(sw, sh) embedded at the far corner of a width x height picture: the MB records of
+    the small sweep, moved by (width - sw, height - sh) with their vectors, flags and words as they
+    are, so every tap of the sweep reads the same place of its window, now at the largest tile
+    columns (or bands) of the large reference, and the sweep's right and bottom edge contacts are
+    the large picture's.  Outside the window the two anchors are textured over the whole plane
+    (textured_picture_np's recipe) and every other picture predicts with the zero vector in its
+    own directions, without residual.  Returns a SweepBatch (its coverage: the window's)."""
+    ck = (width, height, cf, sw, sh)
+    if ck in _corner:
+        return _corner[ck]
+    s = mc_sweep(sw, sh, cf)
+    mbw, mbh, smw, smh = width // 16, height // 16, sw // 16, sh // 16
+    x0, y0 = mbw - smw, mbh - smh
+    assert x0 % 8 == 0  # the words carry their MB's column mod 8
+    n, sn = mbw * mbh, smw * smh
+    T = _Builder(width, height, cf, 4000 + cf)
+    T.textured_picture_np(1)
+    T.textured_picture_np(2, 0)
+    _, tm, tc = T.finish()
+    inside = ((tm["x"][:n] >= x0) & (tm["y"][:n] >= y0))
+    where = np.nonzero(inside)[0]  # raster order, as the small picture's MBs
+    assert len(where) == sn
+    pics = np.zeros(len(s.pics), R.PIC_DTYPE)
+    mbs = np.zeros(len(s.pics) * n, R.MB_DTYPE)
+    words = []
+    for p in range(len(s.pics)):
+        pics[p] = s.pics[p]
+        pics[p]["mb_first"], pics[p]["mb_width"], pics[p]["mb_height"] = p * n, mbw, mbh
+        M = mbs[p * n:(p + 1) * n]
+        small = s.mbs[p * sn:(p + 1) * sn]
+        if p < 2:
+            M[:] = tm[p * n:(p + 1) * n]
+        else:
+            M["x"], M["y"], M["qscale"] = tm["x"][:n], tm["y"][:n], 2
+            uf, ub = picture_uses(s.pics, s.mbs, p)
+            M["flags"] = (MB_FWD if uf else 0) | (MB_BWD if ub else 0)
+        M["ncoef"][where] = small["ncoef"]
+        for k in ("flags", "cbp", "qscale", "mv"):
+            M[k][where] = small[k]
+        # the words in raster order: the window's MBs take the small sweep's
+        if p < 2:
+            per, o = int(tm["ncoef"][p * n]), int(tm["coef_off"][p * n])
+            big = tc[o:o + n * per].reshape(n, per)
+            rows = [big[i] for i in range(n)]
+        else:
+            rows = [np.zeros(0, np.uint32)] * n
+        for j, i in enumerate(where):
+            o = int(small["coef_off"][j])
+            rows[i] = s.coefs[o:o + int(small["ncoef"][j])]
+        words.append(np.concatenate(rows))
+    nc = mbs["ncoef"].astype(np.int64)
+    mbs["coef_off"] = np.cumsum(nc) - nc
+    out = SweepBatch.__new__(SweepBatch)
+    out.width, out.height, out.cf = width, height, cf
+    out.pics, out.mbs, out.coefs = pics, mbs, np.concatenate(words).astype(np.uint32)
+    out.first_two_dir = s.first_two_dir
+    out.window = (x0, y0)
+    out.coverage = sweep_coverage(width, height, cf, pics, mbs, window=out.window)
+    _corner[ck] = out
+    return out

@@ -93,6 +93,11 @@ def _required_events():
     ev += [f"slice_ext:{i}:{n}" for i in (0, 1) for n in (0, 1, 3)]
     ev += [f"stuffing_bits:{n}" for n in range(8)] + [f"zero_bytes:{n}" for n in range(4)]
     ev += ["last_mb_byte_aligned"]
+    # sizes above 4095 (6.2.2.3 horizontal_size_extension, vertical_size_extension) and slices below
+    # row 127 (6.2.4 slice_vertical_position_extension)
+    ev += [f"hsize_ext:{n}" for n in (1, 2, 3)] + [f"vsize_ext:{n}" for n in (1, 2, 3)]
+    ev += [f"vpos_ext:{n}" for n in range(8)]
+    ev += ["wrap_high:h:9", "wrap_low:h:9"]  # these fit from 8192 wide on (wide_16384)
     return ev
 
 
@@ -189,8 +194,16 @@ class Stream:
     """The writer and the slice-state model.  write(pics) gives the bytes; .mbs and .coefs are the
     expected records in decode order and .events the syntax events met."""
 
-    def __init__(self, name, width, height, cf):
+    def __init__(self, name, width, height, cf, hsize=None, vsize=None, vext=None):
+        """width, height: the coded size.  hsize, vsize: horizontal_size and vertical_size as the
+        headers carry them (14 bits; default the coded size), of which the coded size is the
+        multiple of 16 above.  vext: slices carry slice_vertical_position_extension; the default
+        is the standard's rule, vertical_size > 2800 (6.2.4)."""
         self.name, self.width, self.height, self.cf = name, width, height, cf
+        self.hsize, self.vsize = hsize or width, vsize or height
+        assert (self.hsize + 15) // 16 * 16 == width and (self.vsize + 15) // 16 * 16 == height
+        self.vext = self.vsize > 2800 if vext is None else vext
+        self._negative = False
         self.mbw, self.mbh = width // 16, height // 16
         self.nblocks = {1: 6, 2: 8, 3: 12}[cf]
         self.events = set()
@@ -211,10 +224,19 @@ class Stream:
     def sequence(self):
         b = self.bw
         b.start_code(0xB3)
-        b.put(self.width, 12), b.put(self.height, 12), b.put(1, 4), b.put(3, 4), b.put(0x3FFFF, 18), b.put(1, 1)
-        b.put(0x3FF, 10), b.put(0, 1), b.put(0, 1), b.put(0, 1)
+        # horizontal_size_value, vertical_size_value: the 12 least significant bits (6.3.3)
+        assert self.hsize & 0xFFF and self.vsize & 0xFFF  # (a value of 0 is forbidden)
+        b.put(self.hsize & 0xFFF, 12), b.put(self.vsize & 0xFFF, 12), b.put(1, 4), b.put(3, 4), b.put(0x3FFFF, 18)
+        b.put(1, 1), b.put(0x3FF, 10), b.put(0, 1), b.put(0, 1), b.put(0, 1)
         b.start_code(0xB5)
-        b.put(1, 4), b.put(0x44, 8), b.put(0, 1), b.put(self.cf, 2), b.put(0, 2), b.put(0, 2), b.put(0, 12)
+        # horizontal_size_extension, vertical_size_extension: the 2 most significant bits (6.3.5)
+        b.put(1, 4), b.put(0x44, 8), b.put(0, 1), b.put(self.cf, 2), b.put(self.hsize >> 12, 2), b.put(self.vsize >> 12, 2)
+        b.put(0, 12)
+        if not self._negative:
+            if self.hsize >> 12:
+                self.ev(f"hsize_ext:{self.hsize >> 12}")
+            if self.vsize >> 12:
+                self.ev(f"vsize_ext:{self.vsize >> 12}")
         b.put(1, 1), b.put(0, 8), b.put(0, 1), b.put(0, 2), b.put(0, 5)
         b.start_code(0xB8)
         b.put(0, 25), b.put(1, 1), b.put(0, 1)
@@ -269,7 +291,14 @@ class Stream:
     # ---- one slice (6.2.4) ---------------------------------------------------------------------
     def slice(self, P, y, row):
         b = self.bw
-        b.start_code(y + 1)
+        if self.vext:  # mb_row = (slice_vertical_position_extension << 7) + slice_vertical_position - 1
+            b.start_code((y & 127) + 1)
+            b.put(y >> 7, 3)
+            if not self._negative:
+                self.ev(f"vpos_ext:{y >> 7}")
+        else:
+            assert y < 175
+            b.start_code(y + 1)
         b.put(row.qcode, 5)
         self.ev(f"qcode_slice:{P.qst}:{row.qcode}")
         if row.ext is not None:
@@ -1038,7 +1067,117 @@ def slice_hdr():
     return build(extra)
 
 
+# ---- the geometry limits: sizes above 4095, slices below row 127 ---------------------------------------------
+# REFERENCE: the standard has slice_vertical_position_extension when vertical_size (14 bits) is above
+# 2800 (6.2.4); the reference asks the 12-bit vertical_size_value (mp2v_hdr.h:347, decoder.cpp:119).
+# A coded height of 4096 or more is therefore decodable only through a vertical_size whose low 12
+# bits are above 2800: 8192 as 8191, 12288 as 12287, 16384 as 16383.  neg_vsize_4112 is the other kind.
+def _v(vy, fs=None):
+    return [(0, (0, vy))] if fs is None else [(fs[0], (0, vy)), (fs[1], (0, vy))]
+
+
+def tall(name, width, height, vsize, long_fc):
+    """I, P and B at `width` x `height` (one or two MBs per row): every row is a slice, so every
+    value of slice_vertical_position_extension the height reaches is written.  P: vertical vectors
+    that cross the 128-row boundaries of the extension in both directions (the rows next to each
+    boundary), the longest vectors of vertical f_code long_fc from row 0 and from the last row, and
+    short ones between.  B: bidirectional frame vectors, and field MC with every pair of field
+    selects in the last four rows."""
+    S = Stream(name, width, height, 1, vsize=vsize)
+    rng = _rng(name)
+    f = 1 << (long_fc - 1)
+    mbh = S.mbh
+
+    def first(y, lvl, t, **kw):  # the row's first MB; coded blocks where a one-MB row needs its pattern
+        return pat(S, lvl, t | PAT, **kw) if S.mbw == 1 else MB(t, **kw)
+
+    def rest(lvl, t=0):
+        return [pat(S, lvl, t | PAT, skip=S.mbw - 2, **({"mv": {0: _v(0)}} if t else {}))] if S.mbw > 1 else []
+
+    p_rows, b_rows = [], []
+    for y in range(mbh):
+        if y == 0:
+            vy = 16 * f - 1                        # the longest vector downward (half sample)
+        elif y == mbh - 1:
+            vy = -16 * f                           # the longest upward
+        elif y % 128 == 0:
+            vy = -49                               # 24.5 lines up: across the boundary above
+        elif y % 128 == 127:
+            vy = 47                                # 23.5 lines down: across the boundary below
+        else:
+            vy = (y * 7) % 31 - 15
+        p_rows.append(Row([first(y, 5 + y % 5, FWD, mv={0: _v(vy)})] + rest(-4 - y % 3), qcode=4 + y % 8))
+        if y >= mbh - 4:
+            k = y - (mbh - 4)
+            m = first(y, 6 + k, FWD | BWD, field=True,
+                      mv={0: _v(-6 - 2 * k, (k & 1, k >> 1)), 1: _v(-3 - 2 * k, (k >> 1, 1 - (k & 1)))})
+        else:  # forward from above and backward from below, both from the one side that exists at the ends
+            up, down = -((y * 5) % 29 + 2), (y * 3) % 31 + 1
+            m = first(y, 4 + y % 6, FWD | BWD, mv={0: _v(up if y else down + 2), 1: _v(down if y < mbh - 1 else up - 3)})
+        b_rows.append(Row([m] + rest(5 + y % 4, FWD), qcode=3 + y % 9))
+    pics = [tex_pic(S, rng, fpfd=0), Pic(2, p_rows, fcode=((1, long_fc), (15, 15)), fpfd=0),
+            Pic(3, b_rows, fcode=((1, long_fc), (1, long_fc)), fpfd=0)]
+    return _finish(S, pics)
+
+
+def wide(name, width, height, hsize):
+    """I, P and B with rows of 1024 (1023) MBs.  P: horizontal f_code 9 in its full range, +4095
+    down to +4082 in the first columns, a run of more than 990 skipped macroblocks (30 or more
+    macroblock_escapes), then -4096 up to -4081 in the last columns.  B: the same range in both
+    directions, a wrap below low and one above high under f_code 9 (column 400), a skip run that
+    repeats a bidirectional macroblock 391 times and one that repeats a forward macroblock with
+    the vector -4090."""
+    S = Stream(name, width, height, 1, hsize=hsize)
+    rng = _rng(name)
+    mbw = S.mbw
+    p_rows, b_rows = [], []
+    for y in range(S.mbh):
+        head = [MB(FWD, mv={0: fr(4095 - k, 0)}) for k in range(14)]
+        tail = [MB(FWD, mv={0: fr(-4096 + k, 0)}) for k in range(15)]
+        p_rows.append(Row(head + [pat(S, 7 + y, FWD | PAT, skip=mbw - 30, mv={0: fr(-4096, 0)})] + tail[1:] +
+                          [pat(S, -6 - y)]))
+        head = [MB(FWD | BWD, mv={0: fr(4095 - 2 * k, 0), 1: fr(4094 - 2 * k, 0)}) for k in range(8)]
+        head.append(MB(FWD | BWD, mv={0: fr(3, 0), 1: fr(-1 if y == 0 else 1, 0)}))  # the one the skips repeat
+        # column 400: -4096, +4095 (8191 above it: a wrap below low), -4090 (a wrap above high)
+        mid = [pat(S, 8 - y, BWD | PAT, skip=391, mv={1: fr(-4095, 0)}), MB(FWD, mv={0: fr(-4096, 0)}),
+               MB(FWD, mv={0: fr(4095, 0)}), MB(FWD, mv={0: fr(-4090, 0)})]
+        tail = [MB(BWD if k % 2 else FWD, mv={k % 2: fr(-4096 + 3 * k, 0)}) for k in range(12)]
+        b_rows.append(Row(head + mid + [pat(S, 7 + y, FWD | PAT, skip=mbw - 418, mv={0: fr(-4093, 0)})] +
+                          tail + [pat(S, -5 - y, FWD | PAT, mv={0: fr(-4090, 0)})]))
+    pics = [tex_pic(S, rng), Pic(2, p_rows, fcode=((9, 1), (15, 15))), Pic(3, b_rows, fcode=((9, 1), (9, 1)))]
+    return _finish(S, pics)
+
+
+def size_ext(name, width, height, hsize=None, vsize=None):
+    """an I and a P picture at a size whose extension value no other stream has"""
+    S = Stream(name, width, height, 1, hsize=hsize, vsize=vsize)
+    rng = _rng(name)
+    if S.mbw > 1:
+        rows = [skip_row(S, 5 + y % 4) for y in range(S.mbh)]
+    else:
+        rows = [Row([pat(S, 5 + y % 4, FWD | PAT, mv={0: _v((y * 5) % 9 - 4 if 0 < y < S.mbh - 1 else 0)})])
+                for y in range(S.mbh)]
+    return _finish(S, [tex_pic(S, rng), Pic(2, rows)])
+
+
+LIMIT_BUILDERS = [lambda: tall("tall_16384", 16, 16384, 16383, 9), lambda: tall("tall_8192", 32, 8192, 8191, 8),
+                  lambda: wide("wide_16384", 16384, 16, 16383), lambda: wide("wide_16368", 16368, 32, 16368),
+                  lambda: size_ext("tall_12288", 16, 12288, vsize=12287), lambda: size_ext("wide_4112", 4112, 16),
+                  lambda: size_ext("wide_8208", 8208, 16)]
+LIMIT_NAMES = ["tall_16384", "tall_8192", "wide_16384", "wide_16368", "tall_12288", "wide_4112", "wide_8208"]
+
+
 # ---- negative streams ------------------------------------------------------------------------------------------
+def neg_vsize_4112():
+    """A conforming 16 x 4112 stream: vertical_size 4112 (value 16, extension 1), so every slice
+    carries slice_vertical_position_extension.  REFERENCE: it asks the 12-bit value, 16, reads no
+    extension and takes the extension's bits for the quantiser code: outside its subset."""
+    S = Stream("neg_vsize_4112", 16, 4112, 1)
+    S._negative = True
+    assert S.vext and S.vsize >> 12 == 1 and S.vsize & 0xFFF == 16
+    return _finish(S, [tex_pic(S, _rng(S.name))])
+
+
 def _neg(name):
     S = Stream(name, 64, 32, 1)
     S._negative = True
@@ -1079,6 +1218,7 @@ NEGATIVE = [  # builder, status, reason of the host emitter
     (neg_skip_in_i, -2, "skipped macroblock in an I picture"),
     (neg_cmv_in_p, -2, "concealment motion vectors in a P/B picture"),
     (neg_cmv_in_i, -2, "concealment motion vectors in an I picture"),
+    (neg_vsize_4112, -2, "vertical_size 4112"),
 ]
 
 BUILDERS = ([lambda k=k: fcode4(k) for k in range(5)] +
@@ -1087,7 +1227,7 @@ BUILDERS = ([lambda k=k: fcode4(k) for k in range(5)] +
              lambda: wrap_v("wrap_v_b", (4, 5)), mv_seq, skip_runs, mbtypes, lambda: quant(0), lambda: quant(1),
              cbp420, cbp422, cbp444, lambda: dc(0, 2), lambda: dc(1, 3), lambda: dc(2, 2), lambda: dc(3, 3), coefs] +
             [lambda p=p: piclevel(p) for p in range(4)] + [lambda cf=cf: matrices(cf) for cf in (1, 2, 3)] +
-            [slice_hdr])
+            [slice_hdr] + LIMIT_BUILDERS)
 
 
 def build_all():

@@ -60,6 +60,13 @@ CASES = [
     ("sd480_420_field", 720, 480, 1, dict(n_gops=1, gop_n=6, gop_m=3, frame_pred_frame_dct=0, seed=1745)),
     ("w80_422_field", 80, 48, 2, dict(n_gops=1, gop_n=12, gop_m=3, frame_pred_frame_dct=0, seed=1746)),
     ("w48_444", 48, 32, 3, dict(n_gops=1, gop_n=12, gop_m=3, seed=1747)),
+    # the geometry limits (MP2VG_MAX_DIMENSION): 1024 MB rows, slices in all eight values of
+    # slice_vertical_position_extension, vertical_size 16383 (value 4095, extension 3); and 1024-MB
+    # rows with f_code 9 vectors, horizontal_size 16383.  I, P and B with field MC / DCT.
+    ("tall_16384_420", 16, 16384, 1, dict(n_gops=1, gop_n=3, gop_m=2, leading_b=0, frame_pred_frame_dct=0,
+                                          seed=1748)),
+    ("wide_16384_422", 16384, 16, 2, dict(n_gops=1, gop_n=3, gop_m=2, leading_b=0, frame_pred_frame_dct=0,
+                                          f_code=9, seed=1749)),
 ]
 
 
@@ -74,9 +81,18 @@ def main():
     if not os.path.exists(REF):
         sys.exit("build the reference first: make -C oracle ref")
     os.makedirs(OUT, exist_ok=True)
+    # names on the command line: only those cases are written, the others keep their manifest entry
+    only = set(sys.argv[1:])
+    assert only <= {c[0] for c in CASES}, only
+    kept = {}
+    if only:
+        kept = {e["name"]: e for e in json.load(open(os.path.join(OUT, "manifest.json")))}
     manifest = []
     with tempfile.TemporaryDirectory() as tmp:
         for name, w, h, cf, params in CASES:
+            if only and name not in only:
+                manifest.append(kept[name])
+                continue
             es = generate_es(width=w, height=h, chroma_format=cf, **params)
             path = os.path.join(OUT, name + ".m2v")
             with open(path, "wb") as f:

@@ -64,6 +64,110 @@ def test_frame_geometry_matches_reference_frame_c():
         _lib.geometry(100, 64, 1)
 
 
+def _host_entry_points(w, h, cf, es, pics, mbs, coefs):
+    """Every entry point that takes a config and needs no device, as (name, call) on a w x h
+    config.  The calls raise Mp2vgError when the library refuses."""
+    import numpy as np
+
+    from tiny_mp2v_dec_amd import records as R
+
+    def raw_bytes(fn, desc):
+        cfg, out = _lib.make_config(w, h, cf), ctypes.c_uint64()
+        _lib.check(getattr(_lib.lib(), fn)(ctypes.byref(cfg), ctypes.byref(desc), 1, ctypes.byref(out)), fn)
+        return out.value
+
+    one = np.zeros(1, np.int32)
+    # a tensor export of the far corner (the resize ratio is limited to 32:1)
+    if w > h:
+        size, crop = (224, 8), (max(w - 448, 0), 0, min(w, 448), 16)
+    else:
+        size, crop = (8, 224), (0, max(h - 448, 0), 16, min(h, 448))
+    return [
+        ("mp2vg_frame_geometry", lambda: _lib.geometry(w, h, cf)),
+        ("mp2vg_parse_es", lambda: R.Parsed(es, w, h, cf)),
+        ("mp2vg_scan_es", lambda: R.Scan(es, w, h, cf).close()),
+        ("mp2vg_batch_validate", lambda: R.plan_batch(w, h, cf, len(pics), pics, mbs, coefs)),
+        ("mp2vg_batch_plan", lambda: R.plan_dump(w, h, cf, len(pics), pics, mbs, coefs)),
+        ("mp2vg_export_bytes", lambda: raw_bytes("mp2vg_export_bytes", _lib.make_export())),
+        ("mp2vg_tensor_bytes", lambda: raw_bytes("mp2vg_tensor_bytes", _lib.make_tensor(size, crop))),
+        ("mp2vg_tensor_items_plan",
+         lambda: R.items_plan(w, h, cf, size, [crop])),
+        ("mp2vg_motion_bytes", lambda: R.motion_bytes(w, h, cf, 1)),
+        ("mp2vg_motion_records", lambda: R.motion_host(pics, mbs, coefs, w, h, cf, order=one)),
+        ("mp2vg_residual_bytes", lambda: R.residual_bytes(w, h, cf, 1)),
+        ("mp2vg_residual_records", lambda: R.residual_host(pics, mbs, coefs, w, h, cf, order=one)),
+    ]
+
+
+def _i_picture(w, h, cf):
+    from tiny_mp2v_dec_amd import records as R
+    es = R.generate_es(width=w, height=h, chroma_format=cf, n_gops=1, gop_n=1, gop_m=1, seed=16384 + cf)
+    p = R.Parsed(es, w, h, cf)
+    return es, p.pics, p.mbs, p.coefs
+
+
+def test_geometry_limit_slot_sizes():
+    """MP2VG_MAX_DIMENSION: 16384 is accepted in either dimension and in both, with the slot size
+    the frame_c formula gives; the header's constant is the one the library applies."""
+    text = open(os.path.join(REPO, "include", "mp2vg.h")).read()
+    assert re.search(r"#define\s+MP2VG_MAX_DIMENSION\s+16384\b", text)
+    for cf, chroma in ((1, 0.5), (2, 1.0), (3, 2.0)):
+        for w, h in ((16384, 16), (16, 16384), (16384, 16384)):
+            pw, ph, st, slot = _lib.geometry(w, h, cf)
+            s0 = (w + 63) & ~63
+            s1 = s0 if cf == 3 else ((s0 >> 1) + 63) & ~63
+            assert st == [s0, s1, s1]
+            assert slot == s0 * h + 2 * s1 * (h // 2 if cf == 1 else h)
+            if w == h:
+                assert slot == int(16384 * 16384 * (1 + chroma))
+    assert _lib.geometry(16384, 16384, 3)[3] == 805306368
+
+
+@pytest.mark.parametrize("size", [(16384, 16), (16, 16384)], ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("cf", [1, 2, 3])
+def test_geometry_limit_accepted_by_every_host_entry_point(size, cf):
+    """A 1024-MB row and 1024 one-MB rows (one I picture from the stream writer) pass every host-only
+    entry point that takes a config."""
+    w, h = size
+    es, pics, mbs, coefs = _i_picture(w, h, cf)
+    assert (int(pics[0]["mb_width"]), int(pics[0]["mb_height"]), len(mbs)) == (w // 16, h // 16, 1024)
+    for name, call in _host_entry_points(w, h, cf, es, pics, mbs, coefs):
+        call()
+
+
+@pytest.mark.parametrize("size", [(16400, 16), (16, 16400), (1 << 20, 16), (16, 1 << 20), (1 << 20, 1 << 20)],
+                         ids=lambda s: "%dx%d" % s)
+def test_geometry_above_the_limit_refused_by_every_host_entry_point(size):
+    """16400 and 1 << 20 in either dimension: MP2VG_E_INVALID with a message that names the limit,
+    from every host-only entry point that takes a config, before any record or stream byte is read
+    (the records and the stream are those of a 16 x 16 picture)."""
+    w, h = size
+    es, pics, mbs, coefs = _i_picture(16, 16, 1)
+    for name, call in _host_entry_points(w, h, 1, es, pics, mbs, coefs):
+        if name in ("mp2vg_motion_records", "mp2vg_residual_records") and w * h > 1 << 26:
+            continue  # the wrapper would allocate the output planes of the refused size first
+        with pytest.raises(_lib.Mp2vgError, match="16384") as e:
+            call()
+        assert e.value.status == -1, name  # MP2VG_E_INVALID
+
+
+def test_stream_writer_sizes():
+    """The stream writer reaches 16384 in either dimension and refuses what no stream can carry: a
+    size above 16384, and a height above 2800 that the reference's slice-extension rule (the 12-bit
+    vertical_size_value above 2800) cannot address."""
+    from tiny_mp2v_dec_amd import records as R
+    for w, h in ((16400, 16), (16, 16400), (16, 4112), (16, 6896), (16, 8208)):
+        with pytest.raises(_lib.Mp2vgError) as e:
+            R.generate_es(width=w, height=h, chroma_format=1, n_gops=1, gop_n=1, gop_m=1)
+        assert e.value.status == -1, (w, h)
+    for w, h, hs, vs in ((16384, 16, 16383, 16), (16368, 32, 16368, 32), (16, 16384, 16, 16383), (32, 8192, 32, 8191),
+                         (16, 2816, 16, 2816), (4096, 16, 4095, 16), (16, 6912, 16, 6912)):
+        es = R.generate_es(width=w, height=h, chroma_format=1, n_gops=1, gop_n=1, gop_m=1)
+        hd = R.Parsed(es, w, h, 1).headers
+        assert (hd.sequence_header.horizontal_size_value | hd.sequence_extension.horizontal_size_extension << 12,
+                hd.sequence_header.vertical_size_value | hd.sequence_extension.vertical_size_extension << 12) == (hs, vs)
+
+
 def test_invalid_arguments_rejected():
     L = _lib.lib()
     assert L.mp2vg_create(None, None) == -1

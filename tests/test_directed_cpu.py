@@ -218,6 +218,181 @@ def test_row_width_batches_validate(cf, size):
     assert {(w // 16) % 4 for w, _ in ROW_WIDTH_SIZES} == {0, 1, 2, 3}
 
 
+# ---- the batches of tests/test_gpu_limits.py ---------------------------------------------------------
+
+LIMIT_W, LIMIT_W1, LIMIT_T, LIMIT_T1 = (16384, 32), (16368, 32), (32, 16384), (16, 16384)
+
+
+@pytest.mark.parametrize("cf", [1, 2, 3])
+@pytest.mark.parametrize("size", [LIMIT_W, LIMIT_W1, LIMIT_T, LIMIT_T1], ids=_size_id)
+def test_limit_row_width_batches(cf, size):
+    """row_width_batch at the limit sizes passes the upload validation and plans into I, P and B
+    (or mixed) launches; its records reach MB column 1023 (1022 at 16368) or MB row 1023, and
+    hold intra, forward, backward, bidirectional and field-MC MBs in the last eight MBs' columns
+    or rows."""
+    w, h = size
+    pics, mbs, coefs = D.row_width_batch(w, h, cf)
+    of_pic, modes = R.plan_batch(w, h, cf, 5, pics, mbs, coefs)
+    assert modes[of_pic[0]] == 0 and modes[of_pic[1]] == 1 and {int(modes[of_pic[p]]) for p in (2, 3, 4)} <= {2, 3}
+    assert int(mbs["x"].max()) == w // 16 - 1 and int(mbs["y"].max()) == h // 16 - 1
+    far = mbs[(mbs["x"] >= w // 16 - 8) & (mbs["y"] >= h // 16 - 8)]
+    fl = far["flags"].astype(np.int64)
+    assert (fl & _lib.MB_INTRA).any() and (fl & _lib.MB_FIELD_MC).any()
+    inter = fl[(fl & _lib.MB_INTRA) == 0] & (_lib.MB_FWD | _lib.MB_BWD)
+    assert {_lib.MB_FWD, _lib.MB_BWD, _lib.MB_FWD | _lib.MB_BWD} <= set(inter.tolist())
+
+
+@pytest.mark.parametrize("cf", [1, 2, 3])
+@pytest.mark.parametrize("size", [LIMIT_W, LIMIT_W1], ids=_size_id)
+def test_limit_long_vector_batch(cf, size):
+    """+-(2 * (width - 16) - 1) at the two ends of the row (32735 at 16384: int16's end but 32),
+    stepped through between, frame MC in row 0 and field MC in row 1, forward in the P picture and
+    in both directions in the B picture, on textured anchors."""
+    w, h = size
+    pics, mbs, coefs = D.long_vector_batch(w, h, cf)
+    of_pic, modes = R.plan_batch(w, h, cf, len(pics), pics, mbs, coefs)
+    assert [int(modes[of_pic[p]]) for p in range(4)] == [0, 1, 1, 2]
+    n, mbw, far = (w // 16) * (h // 16), w // 16, 2 * (w - 16) - 1
+    for p in (2, 3):
+        for row in (0, 1):
+            m = mbs[p * n + row * mbw:p * n + (row + 1) * mbw]
+            assert ((m["flags"] & _lib.MB_FIELD_MC) != 0).all() == (row == 1)
+            fwd = (m["flags"] & _lib.MB_FWD) != 0
+            vx = m["mv"][:, 0, 0, 0].astype(int)[fwd]
+            assert vx[0] == far and (np.diff(vx) < 0).all() and vx[-1] <= -far + 64, (p, row)
+    bx = mbs["mv"][3 * n:4 * n, 0, 1, 0].astype(int)
+    assert bx.max() >= far - 64 and bx.min() <= -far + 63
+    frames = D.expected_frames(("long", w, h, cf), w, h, cf, pics, mbs, coefs)
+    _assert_textured_references(frames, pics, "long")
+
+
+@pytest.mark.parametrize("cf", [1, 2, 3])
+@pytest.mark.parametrize("size", [LIMIT_T, (48, 4128)], ids=_size_id)
+def test_limit_long_vertical_batch(cf, size):
+    """Per coverage key (7 tap modes x 5 MC types), recomputed from the records: the largest and
+    the smallest mvy.  The stepped vector loses 2 * far / (mbh - 1) per MB row, and every key
+    comes round within 24 rows of either end (frame / field alternate, the MB kinds of the
+    two-direction picture have period 3, the field selects period 8), so each key must hold a
+    vector within 48 / (mbh - 1) of the longest legal one in both signs; the longest itself
+    (+-32735 frame, +-16367 field at 16384 lines) is applied in row 0 and in the last row."""
+    w, h = size
+    pics, mbs, coefs = D.long_vertical_batch(w, h, cf)
+    of_pic, modes = R.plan_batch(w, h, cf, len(pics), pics, mbs, coefs)
+    assert [int(modes[of_pic[p]]) for p in range(6)] == [0, 1, 1, 1, 3, 3]
+    cov = D.long_vertical_coverage(w, h, pics, mbs)
+    mbh = h // 16
+    print("\n%dx%d cf %d: largest / smallest mvy per key" % (w, h, cf))
+    for key in D.KEYS:
+        far = D.long_vertical_far(h, key[1] != 0)
+        hi, lo = cov[key]
+        print("%-40s %+6d %+6d of +-%d" % (D.key_name(key), hi, lo, far))
+        assert hi <= far and lo >= -far
+        assert hi >= far * (1 - 48 / (mbh - 1)) and lo <= -far * (1 - 48 / (mbh - 1)), D.key_name(key)
+    for t in (0, 1, 2):  # the P loop's pictures: the longest vector itself, frame and field
+        assert cov[(t, 0)] == (D.long_vertical_far(h, False), -D.long_vertical_far(h, False))
+        assert max(cov[(t, c)][0] for c in (1, 2, 3, 4)) == D.long_vertical_far(h, True)
+        assert min(cov[(t, c)][1] for c in (1, 2, 3, 4)) == -D.long_vertical_far(h, True)
+    if h == 16384:
+        assert D.long_vertical_far(h, False) == 32735 and D.long_vertical_far(h, True) == 16367
+    frames = D.expected_frames(("vertical", w, h, cf), w, h, cf, pics, mbs, coefs)
+    _assert_textured_references(frames, pics, "vertical")
+
+
+@pytest.mark.parametrize("cf", [1, 2, 3])
+@pytest.mark.parametrize("case", [LIMIT_W + (128, 32), LIMIT_T + (32, 64)], ids=lambda c: "%dx%d" % c[:2])
+def test_limit_corner_sweep_coverage(case, cf):
+    """sweep_coverage restricted to the window at the far corner (the last 8 MB columns of
+    16384 x 32, the last 4 MB rows of 32 x 16384): each of the 35 keys holds all 64 x-phase and all
+    64 y-phase pairs and both signs, and touches the picture's bottom edge (frame MC: and its right
+    edge) with and without the half-pel flag, in luma and, with the chroma half-pel flag, in
+    chroma; the anchors are textured over the whole plane; the batch passes the upload validation."""
+    w, h, sw, sh = case
+    s = D.corner_sweep(w, h, cf, sw, sh)
+    R.plan_batch(w, h, cf, len(s.pics), s.pics, s.mbs, s.coefs)
+    assert s.window == (w // 16 - sw // 16, h // 16 - sh // 16)
+    for key in D.KEYS:
+        c, name = s.coverage[key], D.key_name(key)
+        assert c["xphase"] == c["yphase"] == {(a, b) for a in range(32) for b in range(2)}, name
+        assert {-1, 1} <= c["sx"] and {-1, 1} <= c["sy"], name
+        want = {"B0", "B1"} | ({"R0", "R1"} if key[1] == 0 else set())
+        assert want <= {n for pl, n in c["contacts"] if pl == 0}, (name, c["contacts"])
+        for pl in (1, 2):
+            assert {(pl, "R1"), (pl, "B1")} <= c["contacts"], (name, pl)
+    frames = D.expected_frames(("corner", w, h, cf), w, h, cf, s.pics, s.mbs, s.coefs)
+    _assert_textured_references(frames, s.pics, "corner")
+
+
+@pytest.mark.parametrize("cf", [1, 2, 3])
+@pytest.mark.parametrize("kind", ["I", "P", "B"])
+def test_limit_word_count_batch(cf, kind):
+    """At 16384 x 16 the 256 groups of the one row hold every required total."""
+    w, h = 16384, 16
+    pics, mbs, coefs = D.word_count_batch(w, h, cf, kind)
+    R.plan_batch(w, h, cf, len(pics), pics, mbs, coefs)
+    p = len(pics) - 1
+    assert int(pics[p]["picture_coding_type"]) == {"I": 1, "P": 2, "B": 3}[kind]
+    groups = D.group_totals(w, h, pics, mbs, p)
+    assert len(groups) == 256 and all(nmb == 4 for nmb, _, _ in groups)
+    assert set(D.required_totals(cf, kind)) <= {t for _, t, _ in groups}
+
+
+@pytest.mark.parametrize("size,cf", [((320, 288), 3), ((336, 256), 1), ((320, 272), 2)])
+def test_sparse_frame_expected_is_the_oracles_frame(size, cf):
+    """sparse_frame_expected (zero-vector MBs from their definition, the directed MBs alone through
+    the oracle) gives the bytes the oracle gives on the whole batch, at sizes where that is cheap:
+    what tests/test_gpu_limits.py compares the 16384 x 16384 frame with."""
+    from helpers import SlotOracle
+    w, h = size
+    pics, mbs, coefs, directed = D.sparse_frame_batch(w, h, cf)
+    R.plan_batch(w, h, cf, 4, pics, mbs, coefs)
+    full, short = SlotOracle(w, h, cf, 4), SlotOracle(w, h, cf, 4)
+    sb = int(full.g.slot_bytes)
+    full.pool[:2 * sb] = short.pool[:2 * sb] = D.textured_bytes(np.random.default_rng(5), 2 * sb)
+    full.decode(pics, mbs, coefs)
+    D.sparse_frame_expected(short, pics, mbs, coefs, directed)
+    for s in range(4):
+        for a, b in zip(full.planes(s), short.planes(s)):
+            assert np.array_equal(a, b), s
+    assert not np.array_equal(full.planes(2)[0], full.planes(0)[0])  # the directed MBs changed something
+
+
+def test_sparse_frame_batch_at_the_largest_size():
+    """At 16384 x 16384, 4:4:4: the batch passes the upload validation as one mixed launch; the
+    directed MBs sit in the four corners and in the last MB row, hold frame and field MC, all three
+    direction kinds and residuals, and the two longest vectors; some tap reads the last tile band
+    of the Cr plane (rows from 16380), the end of the tile slot."""
+    w, h, cf = 16384, 16384, 3
+    pics, mbs, coefs, directed = D.sparse_frame_batch(w, h, cf)
+    assert R.plan_batch(w, h, cf, 4, pics, mbs, coefs)[1].tolist() == [3]
+    assert _lib.geometry(w, h, cf)[3] == 805306368
+    n = 1 << 20
+    for p in range(2):
+        d = mbs[directed[p]]
+        corners = {(int(x) >= 512, int(y) >= 512) for x, y in zip(d["x"], d["y"])}
+        assert len(corners) == 4 and (d["y"] == 1023).sum() > 200
+        fl = d["flags"].astype(np.int64)
+        assert (fl & _lib.MB_FIELD_MC).any() and not (fl & _lib.MB_FIELD_MC).all() and (d["ncoef"] > 0).sum() > 100
+        if p:
+            assert {int(f) & 6 for f in fl} == {2, 4, 6}
+        rest = np.ones(n, bool)
+        rest[directed[p] - p * n] = False
+        m = mbs[p * n:(p + 1) * n][rest]
+        assert not m["mv"].any() and not m["ncoef"].any() and (m["flags"] == (2 if p == 0 else 6)).all()
+        last_rows = 0
+        for i in directed[p]:
+            f = int(mbs["flags"][i])
+            field = bool(f & _lib.MB_FIELD_MC)
+            for r in range(2 if field else 1):
+                for s in range(2):
+                    if f & (_lib.MB_FWD, _lib.MB_BWD)[s]:
+                        vx, vy = (int(v) for v in mbs["mv"][i, r, s])
+                        fs = 1 if f & _lib.mb_fs_bit(r, s) else 0
+                        y1 = D.tap_rect(w, h, cf, 2, int(mbs["x"][i]), int(mbs["y"][i]), vx, vy, field, fs)[3]
+                        last_rows += y1 >= h - 4
+        assert last_rows > 0
+    assert tuple(mbs["mv"][0, 0, 0]) == (32735, 32735) and tuple(mbs["mv"][n - 1, 0, 0])[0] == -32736
+
+
 def _one_mb_batch(w, h, cf, x, y, field, fs, vec):
     """An I picture and a P picture whose MB (x, y) applies `vec` (field MC: as both vectors, with
     field select fs); every other MB the zero vector."""

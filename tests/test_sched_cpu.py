@@ -125,6 +125,43 @@ def test_c1_i_only_plan_covers_cross_row_slices():
     assert set(dump["launches"][:, 2].tolist()) == {0}
 
 
+LIMIT_SIZES = [(16384, 32), (16368, 32), (32, 16384), (16, 16384)]
+
+
+@pytest.mark.parametrize("one_stream", [False, True], ids=["two_streams", "one_stream"])
+@pytest.mark.parametrize("size", LIMIT_SIZES, ids=lambda s: "%dx%d" % s)
+def test_limit_geometries_plan_correctly(size, one_stream):
+    """An I, P, B batch and an I-only batch at the sizes of tests/test_gpu_limits.py, in the three
+    chroma formats: the plan meets every requirement (check_plan), and from the dump: every P and
+    B slice is one whole row, of 1024 (1023) MBs or, at 32 and 16 wide, of 2 and 1 (1024 slices per
+    picture); the P and B launches pair their slices (mates) at 16384 alone, where a row is a
+    multiple of the 4-MB group.  I slices, on one stream and on two, in both batches: the planner's
+    slice of an I launch is one row, two rows in 4:4:4 where a row is a multiple of the group
+    (runtime.cpp rows_i), so at 16384 x 32 in 4:4:4 every I slice runs across both rows of its
+    picture (2048 MBs), and everywhere else (4:2:0 and 4:2:2 there; every format at 16368 x 32,
+    32 x 16384 and 16 x 16384) every I slice is exactly one row.  The cut on group boundaries
+    inside a row (i_slice_groups, test_c1_i_only_plan_covers_cross_row_slices) is chosen at none of
+    these sizes: every I slice starts on a row and holds whole rows."""
+    w, h = size
+    mbw, mbh = w // 16, h // 16
+    ipb = [D.pic("I", 0), D.pic("P", 1, 0), D.pic("B", 2, 0, 1)]
+    for cf in (1, 2, 3):
+        rows_i = 2 if cf == 3 and mbw % 4 == 0 else 1
+        for spec in (ipb, [D.pic("I", p) for p in range(4)]):
+            pics, mbs, coefs, uses = D.build(w, h, cf, spec, seed=16384 + cf, dense=False)
+            dump = _plan_and_check(spec, pics, mbs, coefs, uses, (w, h, cf), one_stream)
+            sl = dump["slices"]
+            assert int(sl[:, 2].sum()) == len(spec) * mbw * mbh
+            for L in dump["launches"]:
+                s = sl[int(L[0]):int(L[1])]
+                if int(L[2]) == 0:
+                    assert (s[:, 2] == rows_i * mbw).all() and (s[:, 1] % (rows_i * mbw) == 0).all(), (size, cf)
+                    assert int(L[5]) == 0
+                    continue
+                assert (s[:, 2] == mbw).all() and (s[:, 1] % mbw == 0).all() and len(s) % mbh == 0
+                assert int(L[5]) == (2 if mbw % 4 == 0 else 0), (size, cf, L.tolist())
+
+
 @pytest.mark.parametrize("name", sorted(D.DIRECTED) + ["units5"])
 def test_oracle_is_indexed_by_slot(name):
     """Decoding the prefix pics[:k] gives, for every slot picture k - 1 does not write, the bytes

@@ -56,7 +56,10 @@ def test_fixture_is_what_the_writer_writes(streams):
         S = build()
         e = BY_NAME[S.name]
         assert read(e) == S.es and (e["status"], e["reason"]) == (status, reason)
-    total = sum(os.path.getsize(os.path.join(SYNTAX, n)) for n in os.listdir(SYNTAX))
+    # the streams at the geometry limits: under 400 KB each and 1 MB together; all others 256 KB together
+    limit = {n + ".m2v": os.path.getsize(os.path.join(SYNTAX, n + ".m2v")) for n in DS.LIMIT_NAMES}
+    assert max(limit.values()) < 400 * 1024 and sum(limit.values()) < 1024 * 1024
+    total = sum(os.path.getsize(os.path.join(SYNTAX, n)) for n in os.listdir(SYNTAX) if n not in limit)
     assert total < 256 * 1024
 
 

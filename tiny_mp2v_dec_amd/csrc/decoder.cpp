@@ -252,6 +252,7 @@ extern "C" int mp2vg_decoder_create_multi(const mp2vg_config_t* cfg, const int32
         set_error("unknown decoder flags in mp2vg_config_t.reserved");
         return MP2VG_E_INVALID;
     }
+    if (mp2vg_frame_geometry(cfg, nullptr, nullptr, nullptr, nullptr) != MP2VG_OK) return MP2VG_E_INVALID;
     auto* d = new mp2vg_decoder();
     d->cfg = *cfg;
     // chunk k decodes into its own slots while chunk k-1 is still being downloaded

@@ -58,12 +58,29 @@ struct PicParams {
     uint8_t qme[4][64];
 };
 
+// horizontal_size (14 bits) of a coded width: the width itself, or one less where its low 12 bits
+// would be the forbidden horizontal_size_value 0 (16384 is written as 16383).
+static int gen_horizontal_size(int width) { return (width & 0xfff) ? width : width - 1; }
+
+// vertical_size (14 bits) of a coded height, or -1.  The reference reads
+// slice_vertical_position_extension iff the 12-bit vertical_size_value is above 2800, so a coded
+// height above 2800 (more than 175 MB rows) needs a vertical_size in (height - 16, height] whose low
+// 12 bits are above 2800: 8192 is written as 8191, 16384 as 16383, and 4112 cannot be written.
+static int gen_vertical_size(int height) {
+    if (height <= 2800) return height;
+    for (int v = std::min(height, 16383); v > height - 16; v--)
+        if ((v & 0xfff) > 2800) return v;
+    return -1;
+}
+
 class Writer {
 public:
     Writer(const mp2vg_gen_params_t& p) : P(p), rng(p.seed) {
         g.init(p.width, p.height, p.chroma_format);
         mbw = p.width / 16;
         mbh = p.height / 16;
+        hsize = gen_horizontal_size(p.width);
+        vsize = gen_vertical_size(p.height);
     }
     int run(std::vector<uint8_t>& out);
 
@@ -72,6 +89,7 @@ private:
     Rng rng;
     Geom g;
     int mbw, mbh;
+    int hsize, vsize;  // horizontal_size, vertical_size (14 bits) as the headers carry them
     BitWriter bw;
     Enc enc;
 
@@ -92,8 +110,8 @@ private:
 
 void Writer::sequence_header() {
     bw.start_code(0xB3);
-    bw.put(P.width & 0xfff, 12);
-    bw.put(P.height & 0xfff, 12);
+    bw.put(hsize & 0xfff, 12);   // horizontal_size_value, vertical_size_value
+    bw.put(vsize & 0xfff, 12);
     bw.put(1, 4);            // aspect_ratio_information
     bw.put(3, 4);            // frame_rate_code (25)
     bw.put(0x3FFFF, 18);     // bit_rate_value
@@ -107,8 +125,8 @@ void Writer::sequence_header() {
     bw.put(0x44, 8);         // profile_and_level_indication
     bw.put(P.frame_pred_frame_dct ? 1 : 0, 1);  // progressive_sequence
     bw.put(P.chroma_format, 2);
-    bw.put(0, 2);
-    bw.put(0, 2);
+    bw.put(hsize >> 12, 2);      // horizontal_size_extension, vertical_size_extension
+    bw.put(vsize >> 12, 2);
     bw.put(0, 12);
     bw.put(1, 1);
     bw.put(0, 8);
@@ -230,7 +248,7 @@ void Writer::block(const PicParams& pp, bool intra, int b) {
 }
 
 void Writer::slice(const PicParams& pp, int row) {
-    if (P.height > 2800) {
+    if ((vsize & 0xfff) > 2800) {  // the reference's rule: the 12-bit vertical_size_value
         bw.start_code((uint8_t)((row & 127) + 1));
         bw.put(row >> 7, 3);
     } else {
@@ -515,8 +533,16 @@ extern "C" void mp2vg_gen_default_params(mp2vg_gen_params_t* p) {
 extern "C" int mp2vg_generate_es(const mp2vg_gen_params_t* p, uint8_t** out, uint64_t* len) {
     if (!p || !out || !len || p->width <= 0 || p->height <= 0 || (p->width & 15) || (p->height & 15) ||
         p->chroma_format < 1 || p->chroma_format > 3 || p->f_code < 1 || p->f_code > 9 ||
-        p->width > 4095 || p->height > 4095 || p->n_gops < 1)
+        p->width > MP2VG_MAX_DIMENSION || p->height > MP2VG_MAX_DIMENSION || p->n_gops < 1) {
+        mp2vg::set_error("mp2vg_generate_es: bad parameters (sizes are multiples of 16 up to 16384)");
         return MP2VG_E_INVALID;
+    }
+    if (mp2vg::gen_vertical_size(p->height) < 0) {
+        mp2vg::set_error("mp2vg_generate_es: no vertical_size of a " + std::to_string(p->height) +
+                         "-line picture has a 12-bit value above 2800, which the reference needs to read "
+                         "slice_vertical_position_extension");
+        return MP2VG_E_INVALID;
+    }
     std::vector<uint8_t> buf;
     mp2vg::Writer w(*p);
     w.run(buf);

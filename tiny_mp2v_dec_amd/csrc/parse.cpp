@@ -763,6 +763,19 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         set_error("stream chroma_format differs from the decoder configuration");
         return MP2VG_E_UNSUPPORTED;
     }
+    // slice_vertical_position_extension is present iff vertical_size (14 bits) is above 2800 (ISO
+    // 13818-2 6.2.4); the reference asks the 12-bit vertical_size_value instead (mp2v_hdr.h:347), and
+    // so does parse_slice.  Where the two differ (4112 lines: value 16, extension 1) the reference
+    // reads a conforming stream's slices one field off, so such a stream is outside its subset.
+    {
+        const int vsize = C.vertical_size_value | (int)C.hdrs.sequence_extension.vertical_size_extension << 12;
+        if ((vsize > 2800) != (C.vertical_size_value > 2800)) {
+            set_error("vertical_size " + std::to_string(vsize) + ": slices carry slice_vertical_position_extension, "
+                      "which the reference reads only when the 12-bit vertical_size_value (" +
+                      std::to_string(C.vertical_size_value) + ") is above 2800");
+            return MP2VG_E_UNSUPPORTED;
+        }
+    }
     // ---- picture-level validation + W (decoder.cpp:154-192) ----
     for (auto& P : C.pics) {
         PictureHdr& h = P.hdr;

@@ -295,6 +295,13 @@ int mp2vg_frame_geometry(const mp2vg_config_t* cfg, int32_t width[3], int32_t he
         mp2vg::set_error("bad config geometry");
         return MP2VG_E_INVALID;
     }
+    // the largest coded size MPEG-2's 14-bit horizontal_size / vertical_size can carry; the int16
+    // vectors just span it, and every 32-bit slot and tile offset of the kernels stays below 2^31
+    if (cfg->width > MP2VG_MAX_DIMENSION || cfg->height > MP2VG_MAX_DIMENSION) {
+        mp2vg::set_error("bad config geometry: " + std::to_string(cfg->width) + "x" + std::to_string(cfg->height) +
+                         " is above the limit of " + std::to_string(MP2VG_MAX_DIMENSION) + " per dimension");
+        return MP2VG_E_INVALID;
+    }
     mp2vg::Geom g;
     g.init(cfg->width, cfg->height, cfg->chroma_format);
     for (int i = 0; i < 3; i++) {
