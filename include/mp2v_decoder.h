@@ -95,8 +95,10 @@ public:
     mp2v_decoder_c() = default;
     // flags: MP2VG_DECODER_DEVICE_FRAMES hands frames over in HBM (get_planes() then returns
     // device pointers); MP2VG_DECODER_DEVICE_PARSE (= kDeviceParse) parses the slices on the device
-    // instead of on host threads; 0 keeps the reference's host frame_c contract
+    // instead of on host threads; MP2VG_PARSE_CONCEAL (= kConceal) replaces damaged macroblock rows
+    // instead of failing decode() (damage_count()); 0 keeps the reference's host frame_c contract
     static constexpr int kDeviceParse = MP2VG_DECODER_DEVICE_PARSE;
+    static constexpr int kConceal = MP2VG_PARSE_CONCEAL;
     mp2v_decoder_c(const decoder_config_t& config, std::function<void(frame_c*)> renderer, int device = 0,
                    int flags = 0) {
         decoder_init(config, renderer, device, flags);
@@ -145,6 +147,8 @@ public:
         m_group_of_pictures_header = h.have_group_of_pictures_header ? &m_gop : nullptr;
         return true;
     }
+    // rows replaced in the last decode() (kConceal)
+    int damage_count() const { return m_dec ? mp2vg_decoder_damage_count(m_dec) : 0; }
     // reference decoder.h:100: submits the last picture and drains the output.  decode() already
     // does both before it returns, so there is never anything left to flush.
     void flush(mp2v_picture_c* cur_pic = nullptr) { (void)cur_pic; }

@@ -147,6 +147,33 @@ typedef struct mp2vg_config {
  * slices are parsed on the device and no parse workers start.  Display order, the frame pool,
  * host or device frames and the lanes of mp2vg_decoder_create_multi are unchanged. */
 #define MP2VG_DECODER_DEVICE_PARSE 4
+/* mp2vg_config_t.reserved flag (opt-in) for mp2vg_parse_es, mp2vg_scan_es (whose scan carries it to
+ * mp2vg_scan_parse_host and mp2vg_batch_upload_es) and mp2vg_decoder_create / _create_multi: a
+ * damaged slice no longer fails the call.  One definition (sp_conceal_row, csrc/slice_parse.h),
+ * whole rows: a slice rejected for any slice-level reason ("macroblock beyond the end of the row"
+ * .. "slice does not cover the whole macroblock row", whatever its status), or a macroblock row
+ * of a picture that no slice covers, is replaced by a row of mb_width records, and the records the
+ * slice wrote before its fault are discarded:
+ *   P picture   flags = MP2VG_MB_FWD, vectors 0, cbp 0, ncoef 0 (a copy of the reference's row);
+ *   B picture   the same from the forward reference when the picture has one, else MP2VG_MB_BWD
+ *               from the backward reference;
+ *   I picture   with an earlier anchor in decode order (its conceal reference): as a P picture from
+ *               that anchor, and the picture record is re-typed to picture_coding_type 2 with
+ *               fwd_slot = that anchor.  Under the flag every I picture's record carries its conceal
+ *               reference in fwd_slot (-1: none), damaged or not, so that slot lifetimes keep the
+ *               anchor alive; an undamaged I picture keeps type 1 and never reads it;
+ *   no reference at all (the stream's first anchor; a B picture in front of it): intra records
+ *               with every block coded by one DC word of level 1 << (intra_dc_precision + 7), the
+ *               predictor's reset value (mid-grey).
+ * Always qscale 1, reserved 0, coef_off the running word offset.  A concealed missing row's words
+ * follow those of the picture's slices (rows ascending).  Still rejected under the flag: every
+ * picture-level and stream-level fault of pass 1 (a picture without any slice among them), "slice
+ * row outside the picture", "two slices in one macroblock row", and MP2VG_E_INVALID slice-table
+ * entries.  With the flag every anchor but the first depends on the one before it, so the stream
+ * is one shard (mp2vg_parsed_shards returns 1 whenever an I picture has a conceal reference) and a
+ * multi-device decoder runs it on one lane: output never depends on the lane count.  The damage
+ * is reported by mp2vg_parsed_damage / mp2vg_last_upload_damage / mp2vg_decoder_damage_count. */
+#define MP2VG_PARSE_CONCEAL 8
 
 typedef struct mp2vg_ctx mp2vg_ctx_t;
 
@@ -777,8 +804,23 @@ int  mp2vg_parsed_gop_index(const mp2vg_parsed_t* p, int32_t* gop, int32_t n);
  * pictures hold two fields 1/50 or 1/60 s apart (progressive_frame = 0) and which field is the
  * earlier one: what a caller needs to pick the MP2VG_FIELD_* mode of a tensor export.  Returns the
  * number of pictures. */
-enum { MP2VG_PIC_PROGRESSIVE_FRAME = 1, MP2VG_PIC_TOP_FIELD_FIRST = 2, MP2VG_PIC_REPEAT_FIRST_FIELD = 4 };
+enum { MP2VG_PIC_PROGRESSIVE_FRAME = 1, MP2VG_PIC_TOP_FIELD_FIRST = 2, MP2VG_PIC_REPEAT_FIRST_FIELD = 4,
+       /* MP2VG_PARSE_CONCEAL: the picture has a concealed row; it is an I picture whose record was
+        * re-typed to picture_coding_type 2 (it predicts the concealed rows from its conceal reference) */
+       MP2VG_PIC_CONCEALED = 8, MP2VG_PIC_RETYPED_I = 16 };
 int  mp2vg_parsed_picture_flags(const mp2vg_parsed_t* p, uint32_t* flags, int32_t n);
+/* MP2VG_PARSE_CONCEAL: one entry per replaced macroblock row, in stream order (a picture's damaged
+ * slices in stream order, then its missing rows ascending).  pic is relative to the parsed stream
+ * or the uploaded range; status and reason are the rejection the slice would have been
+ * (mp2vg_damage_reason_string(reason) is the text after "picture P slice @O: " of that message);
+ * byte_off is the slice's start code in the stream, or the picture's start code for a missing row. */
+typedef struct mp2vg_damage {
+    int32_t  pic, mb_row, status, reason;
+    uint64_t byte_off;
+} mp2vg_damage_t;
+/* out[0 .. min(*n, max)) are written (out may be NULL with max 0); *n is the true count */
+int  mp2vg_parsed_damage(const mp2vg_parsed_t* p, mp2vg_damage_t* out, int32_t max, int32_t* n);
+const char* mp2vg_damage_reason_string(int32_t reason);
 /* sequence headers of the parsed stream (see mp2vg_stream_headers_t) */
 int  mp2vg_parsed_stream_headers(const mp2vg_parsed_t* p, mp2vg_stream_headers_t* out);
 /* Independent shards for GOP sharding: shard[i] of each picture (decode order), numbered from 0.
@@ -841,6 +883,10 @@ int  mp2vg_batch_download_records(mp2vg_ctx_t* ctx, mp2vg_mb_t* mbs, uint64_t nm
                                   uint64_t ncoefs);
 /* device times (ms, HIP events) of the last mp2vg_batch_upload_es: count pass, scan, emit pass */
 int  mp2vg_last_parse_times(mp2vg_ctx_t* ctx, float ms[3]);
+/* the rows the last mp2vg_batch_upload_es replaced (scan with MP2VG_PARSE_CONCEAL; empty otherwise
+ * and after a clean upload); as mp2vg_parsed_damage, pic relative to the uploaded range.  Damaged I
+ * pictures with a conceal reference were re-typed in the resident picture records. */
+int  mp2vg_last_upload_damage(mp2vg_ctx_t* ctx, mp2vg_damage_t* out, int32_t max, int32_t* n);
 
 /* Conformance hook: decode one Annex B code (MSB-first 64-bit window: the code, then whatever
  * follows) with the emitter's own decoders.  Tables follow the reference's VLC decoders
@@ -929,6 +975,8 @@ int  mp2vg_decoder_frames_allocated(const mp2vg_decoder_t* dec);
  * the blocks.  Any out pointer may be NULL. */
 int  mp2vg_decoder_handoff_stats(const mp2vg_decoder_t* dec, int32_t* in_flight, int32_t* blocks, int32_t* landed,
                                  int32_t* changes);
+/* rows replaced in the last decode() (MP2VG_PARSE_CONCEAL; 0 without it) */
+int  mp2vg_decoder_damage_count(const mp2vg_decoder_t* dec);
 int  mp2vg_decoder_destroy(mp2vg_decoder_t* dec);
 
 #ifdef __cplusplus

@@ -20,6 +20,9 @@ PIC_DTYPE = np.dtype([("dst_slot", "<i4"), ("fwd_slot", "<i4"), ("bwd_slot", "<i
                       ("mb_height", "<u2"), ("alternate_scan", "u1"), ("reserved0", "u1", (3,)),
                       ("temporal_reference", "<i4"), ("W", "u1", (4, 64))])
 assert PIC_DTYPE.itemsize == 288
+DAMAGE_DTYPE = np.dtype([("pic", "<i4"), ("mb_row", "<i4"), ("status", "<i4"), ("reason", "<i4"),
+                         ("byte_off", "<u8")])  # mp2vg_damage_t
+assert DAMAGE_DTYPE.itemsize == 24
 
 MB_INTRA, MB_FWD, MB_BWD, MB_FIELD_MC, MB_DCT_FIELD = 1, 2, 4, 8, 16
 COEF_FIRST1S, COEF_DC = 1 << 29, 1 << 30
@@ -149,6 +152,7 @@ TENSOR_MAX_TAPS = 65
 FIELD_PROGRESSIVE, FIELD_TOP, FIELD_BOTTOM, FIELD_WEAVE = 0, 1, 2, 3  # MP2VG_FIELD_*
 FIELDS = {"progressive": FIELD_PROGRESSIVE, "top": FIELD_TOP, "bottom": FIELD_BOTTOM, "weave": FIELD_WEAVE}
 PIC_PROGRESSIVE_FRAME, PIC_TOP_FIELD_FIRST, PIC_REPEAT_FIRST_FIELD = 1, 2, 4  # MP2VG_PIC_*
+PIC_CONCEALED, PIC_RETYPED_I = 8, 16
 TENSOR_DTYPES = {"uint8": (TENSOR_U8, 1), "float16": (TENSOR_F16, 2), "bfloat16": (TENSOR_BF16, 2),
                  "float32": (TENSOR_F32, 4)}  # name -> (MP2VG_TENSOR_*, element size)
 
@@ -178,6 +182,7 @@ EXPORTS = [
     "mp2vg_batch_download_records", "mp2vg_last_parse_times",
     "mp2vg_motion_bytes", "mp2vg_motion_records", "mp2vg_motion_batch", "mp2vg_last_motion_time",
     "mp2vg_residual_bytes", "mp2vg_residual_records", "mp2vg_residual_batch", "mp2vg_last_residual_time",
+    "mp2vg_parsed_damage", "mp2vg_last_upload_damage", "mp2vg_damage_reason_string", "mp2vg_decoder_damage_count",
 ]
 
 _lib = None
@@ -286,6 +291,10 @@ def lib():
                                    ctypes.c_int),
         "mp2vg_residual_batch": ([VP, P(I32), I32, I32, I32, VP, VP, VP, P(U64)], ctypes.c_int),
         "mp2vg_last_residual_time": ([VP, P(ctypes.c_float)], ctypes.c_int),
+        "mp2vg_parsed_damage": ([VP, VP, I32, P(I32)], ctypes.c_int),
+        "mp2vg_last_upload_damage": ([VP, VP, I32, P(I32)], ctypes.c_int),
+        "mp2vg_damage_reason_string": ([I32], ctypes.c_char_p),
+        "mp2vg_decoder_damage_count": ([VP], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -304,6 +313,7 @@ def check(status, what):
 
 MP2VG_DECODER_DEVICE_FRAMES, MP2VG_CTX_ONE_STREAM = 1, 2  # mp2vg_config_t.reserved flags
 MP2VG_DECODER_DEVICE_PARSE = 4  # drop-in decoder: slices parsed on the device (mp2vg_batch_upload_es)
+MP2VG_PARSE_CONCEAL = 8  # parse / scan / drop-in decoder: damaged rows are replaced, not rejected
 RESIDUAL_DTYPES = {"int16": 0, "int8": 1}  # MP2VG_RESIDUAL_I16 / I8
 RESIDUAL_ZERO_INTRA = 1
 

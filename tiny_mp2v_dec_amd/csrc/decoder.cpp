@@ -234,6 +234,7 @@ struct mp2vg_decoder {
     // (only when the frame pool runs short); lane changes whose lane just left had nothing in
     // flight or was completed by the non-blocking check; lane changes
     int handoffs_in_flight = 0, handoff_blocks = 0, handoffs_landed = 0, lane_changes = 0;
+    int damage_count = 0;  // of the last decode(): rows replaced (MP2VG_PARSE_CONCEAL)
 };
 
 extern "C" int mp2vg_decoder_destroy(mp2vg_decoder_t* d) {
@@ -248,7 +249,7 @@ extern "C" int mp2vg_decoder_create_multi(const mp2vg_config_t* cfg, const int32
                                           mp2vg_render_fn fn, void* user, mp2vg_decoder_t** out) {
     if (!cfg || !fn || !out || !devices || ndevices < 1 || ndevices > 64) return MP2VG_E_INVALID;
     *out = nullptr;
-    if (cfg->reserved & ~(MP2VG_DECODER_DEVICE_FRAMES | MP2VG_DECODER_DEVICE_PARSE)) {
+    if (cfg->reserved & ~(MP2VG_DECODER_DEVICE_FRAMES | MP2VG_DECODER_DEVICE_PARSE | MP2VG_PARSE_CONCEAL)) {
         set_error("unknown decoder flags in mp2vg_config_t.reserved");
         return MP2VG_E_INVALID;
     }
@@ -356,6 +357,8 @@ extern "C" int mp2vg_decoder_handoff_stats(const mp2vg_decoder_t* d, int32_t* in
     return MP2VG_OK;
 }
 
+extern "C" int mp2vg_decoder_damage_count(const mp2vg_decoder_t* d) { return d ? d->damage_count : MP2VG_E_INVALID; }
+
 extern "C" int mp2vg_decoder_frames_allocated(const mp2vg_decoder_t* d) {
     if (!d) return MP2VG_E_INVALID;
     size_t n = d->hpool ? d->hpool->size() : 0;
@@ -398,6 +401,7 @@ static int decoder_decode(mp2vg_decoder_t* d, const uint8_t* buf, uint64_t len) 
     // MP2VG_DECODER_DEVICE_PARSE: the host only scans (start codes, headers, slice table); no parse
     // workers start, and each chunk's slices are parsed on its lane's device (mp2vg_batch_upload_es)
     mp2vg_scan_t* scan = nullptr;
+    d->damage_count = 0;
     if (d->device_parse) {
         const int rc = mp2vg_scan_es(buf, len, &d->cfg, &scan);
         t0 = trace_phase("dropin: scan", t0);
@@ -595,6 +599,8 @@ static int decoder_decode(mp2vg_decoder_t* d, const uint8_t* buf, uint64_t len) 
                 rc = MP2VG_E_UNSUPPORTED;
             }
             t_up += now_ms() - tc;
+            int32_t nd = 0;
+            if (rc == MP2VG_OK && mp2vg_last_upload_damage(L.ctx, nullptr, 0, &nd) == MP2VG_OK) d->damage_count += nd;
         } else {
         tc = now_ms();
         size_t nc = 0;
@@ -602,6 +608,9 @@ static int decoder_decode(mp2vg_decoder_t* d, const uint8_t* buf, uint64_t len) 
             if ((rc = parse_session_wait(ps, p)) != MP2VG_OK) return rc;
             ncoef_of[p - s] = parse_session_ncoefs(ps, p);
             nc += ncoef_of[p - s];
+            // (MP2VG_PARSE_CONCEAL: the worker that finished a damaged I picture re-typed its record)
+            cp[p - s].picture_coding_type = pics[p].picture_coding_type;
+            d->damage_count += parse_session_damage(ps, p);
         }
         t_wait += now_ms() - tc;
         const size_t nm = (size_t)(e - s) * mbs_per_pic;

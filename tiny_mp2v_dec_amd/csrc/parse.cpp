@@ -61,6 +61,8 @@ struct SliceJob {
 struct PicWork {
     PictureHdr hdr;
     int fwd = -1, bwd = -1;   // decode indices of reference pictures (L0 / L1)
+    int conceal_ref = -1;     // I picture: the newest anchor before it (MP2VG_PARSE_CONCEAL)
+    uint64_t byte_off = 0;    // the picture start code
     int gop = -1;
     // a B picture between the first two anchors of a GOP with closed_gop = 1: it predicts only
     // backward (ISO 13818-2 6.3.8), so its forward reference is not a dependency for sharding
@@ -122,6 +124,7 @@ struct SliceOut {
     int mb_row = -1;
     int status = MP2VG_OK;
     std::string err;
+    bool concealed = false;   // MP2VG_PARSE_CONCEAL: the row was replaced (status and err say why)
 };
 
 struct Ctx {
@@ -130,6 +133,7 @@ struct Ctx {
     Geom g;
     int width, height, mbw, mbh;
     int vertical_size_value = 0;
+    bool conceal = false;     // MP2VG_PARSE_CONCEAL
     std::vector<PicWork> pics;
     mp2vg_stream_headers_t hdrs{};
 };
@@ -472,6 +476,7 @@ struct ParsedImpl {
     std::vector<int32_t> shard;  // independent decode-order runs (mp2vg_parsed_shards)
     int32_t nshards = 0;
     mp2vg_stream_headers_t hdrs{};
+    std::vector<mp2vg_damage_t> damage;  // MP2VG_PARSE_CONCEAL: the replaced rows, stream order
 };
 
 }  // namespace mp2vg
@@ -495,6 +500,10 @@ struct ParseSession {
     std::unique_ptr<std::atomic<uint8_t>[]> row_done;  // picture p's rows at [p * mbh, (p + 1) * mbh)
     std::unique_ptr<std::atomic<int>[]> slices_left;   // per picture
     std::vector<size_t> pic_job_begin;
+    // MP2VG_PARSE_CONCEAL, per picture, written by the worker that finishes it: the replacement
+    // rows of its missing rows (ascending; their words follow the slices'), and its damage entries
+    std::vector<std::vector<SliceOut>> extra;
+    std::vector<std::vector<mp2vg_damage_t>> damage;
     std::vector<int> status;  // per picture: 1 pending, else an MP2VG_* status
     std::vector<std::string> err;
     std::mutex mu;
@@ -556,11 +565,71 @@ struct ParseSession {
             if (slices_left[p].fetch_sub(1, std::memory_order_acq_rel) == 1) finish_picture(p);
         }
     }
+    // MP2VG_PARSE_CONCEAL: row `row` of picture p replaced by sp_conceal_row, its words in o
+    bool conceal_row(int p, int row, int status_, int reason, uint64_t byte_off, SliceOut& o) {
+        const PicWork& P = C.pics[p];
+        SpPicHdr h{};
+        h.pct = (uint8_t)P.hdr.pct;
+        h.intra_dc_precision = (uint8_t)P.hdr.intra_dc_precision;
+        h.has_fwd = P.fwd >= 0;
+        h.has_bwd = P.bwd >= 0;
+        h.has_conceal_ref = P.conceal_ref >= 0;
+        SpGeom g{};
+        g.mbw = C.mbw;
+        g.nblocks = C.g.nblocks;
+        if (!o.coefs.reserve((size_t)C.mbw * C.g.nblocks + 1)) return false;
+        struct Out {
+            mp2vg_mb_t* row;
+            uint32_t* words;
+            void record(int x, const mp2vg_mb_t& m) const { row[x] = m; }
+            void word(uint32_t i, uint32_t w) const { words[i] = w; }
+        };
+        uint32_t uses;
+        o.coefs.n = sp_conceal_row(g, h, row, Out{mbs_of(p) + (size_t)row * C.mbw, o.coefs.data()}, uses);
+        o.mb_row = row;
+        o.concealed = true;
+        damage[p].push_back({p, row, status_, reason, byte_off});
+        return true;
+    }
+    static int reason_of(const std::string& text) {
+        for (int r = SP_R_MB_BEYOND_ROW; r <= SP_R_ROW_NOT_WHOLE; r++)
+            if (text == sp_reason_text(r)) return r;
+        return SP_OK;
+    }
     void finish_picture(int p) {
         int st = MP2VG_OK;
         std::string msg;
-        for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1]; j++)  // first failing slice in stream order
-            if (outs[j].status != MP2VG_OK) {
+        if (C.conceal) {  // every slice-level rejection becomes a replacement row, then the missing rows
+            bool nomem = false;
+            for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1] && !nomem; j++) {
+                SliceOut& o = outs[j];
+                const int why = o.status != MP2VG_OK ? reason_of(o.err) : SP_OK;
+                if (why != SP_OK) nomem = !conceal_row(p, o.mb_row, o.status, why, jobs[j].byte_off, o);
+            }
+            bool other = false;
+            for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1]; j++)
+                other = other || (outs[j].status != MP2VG_OK && !outs[j].concealed);
+            if (!other && !nomem) {
+                int missing = 0;
+                for (int r = 0; r < C.mbh; r++) missing += !row_done[(size_t)p * C.mbh + r].load(std::memory_order_relaxed);
+                extra[p].resize(missing);
+                for (int r = 0, k = 0; r < C.mbh && !nomem; r++)
+                    if (!row_done[(size_t)p * C.mbh + r].exchange(1, std::memory_order_relaxed))
+                        nomem = !conceal_row(p, r, MP2VG_E_UNSUPPORTED, SP_R_ROW_UNCOVERED, C.pics[p].byte_off, extra[p][k++]);
+            }
+            if (nomem) {
+                st = MP2VG_E_NOMEM;
+                msg = "out of host memory";
+            } else if (!damage[p].empty()) {
+                res->flags[p] |= MP2VG_PIC_CONCEALED;
+                if (C.pics[p].hdr.pct == 1 && C.pics[p].conceal_ref >= 0) {
+                    res->pics[p].picture_coding_type = 2;  // (fwd_slot holds the conceal reference already)
+                    res->flags[p] |= MP2VG_PIC_RETYPED_I;
+                }
+            }
+        }
+        for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1] && st == MP2VG_OK; j++)  // first failing slice in stream order
+            if (outs[j].status != MP2VG_OK && !outs[j].concealed) {
                 char m[256];
                 snprintf(m, sizeof m, "picture %d slice @%llu: %s", p, (unsigned long long)jobs[j].byte_off,
                          outs[j].err.c_str());
@@ -601,6 +670,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
     C.mbw = cfg->width / 16;
     C.mbh = cfg->height / 16;
     C.g.init(cfg->width, cfg->height, cfg->chroma_format);
+    C.conceal = (cfg->reserved & MP2VG_PARSE_CONCEAL) != 0;
 
     double tp = now_ms();
     // ---- pass 1: start codes and headers, serially (decoder.cpp:278-329) ----
@@ -728,6 +798,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
             gop_anchors = 0;
         } else if (code == 0x00) {  // picture_start_code (decoder.cpp:294-305)
             PicWork pw;
+            pw.byte_off = off;
             pw.hdr.temporal_reference = (int)br.read(10);
             pw.hdr.pct = (int)br.read(3);
             pw.gop = gop < 0 ? 0 : gop;
@@ -736,6 +807,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
                 return MP2VG_E_UNSUPPORTED;
             }
             int idx = (int)C.pics.size();
+            if (pw.hdr.pct == 1) pw.conceal_ref = ref_frames[1];
             if (pw.hdr.pct != 3) {
                 pw.fwd = ref_frames[1];  // I/P: dependency on the newest anchor (L0)
                 ref_frames[0] = ref_frames[1];
@@ -817,7 +889,9 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         memset(&d, 0, sizeof d);
         const PicWork& P = C.pics[p];
         d.dst_slot = p;
-        d.fwd_slot = P.fwd;
+        // (MP2VG_PARSE_CONCEAL: an I picture's record carries its conceal reference, which only a
+        // re-typed, damaged one reads; consumers keep that anchor's slot alive through it)
+        d.fwd_slot = C.conceal && P.hdr.pct == 1 ? P.conceal_ref : P.fwd;
         d.bwd_slot = P.hdr.pct == 3 ? P.bwd : -1;
         d.picture_coding_type = P.hdr.pct;
         d.mb_first = (uint32_t)(mbs_per_pic * p);
@@ -841,6 +915,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         for (int p = npics - 1; p >= 0; p--) {
             const PicWork& P = C.pics[p];
             if (P.fwd >= 0 && !P.closed_leading_b) lo = std::min(lo, (int32_t)P.fwd);
+            if (C.conceal && P.conceal_ref >= 0) lo = std::min(lo, (int32_t)P.conceal_ref);
             if (P.hdr.pct == 3 && P.bwd >= 0) lo = std::min(lo, (int32_t)P.bwd);
             starts[p] = lo >= p;
         }
@@ -901,6 +976,8 @@ int parse_session_start(const uint8_t* buf, uint64_t len, const mp2vg_config_t* 
         }
         S->pic_job_begin[npics] = j;
     }
+    S->extra.resize(npics);
+    S->damage.resize(npics);
     S->status.assign(npics, 1);
     S->err.assign(npics, std::string());
     int nthreads = threads > 0 ? threads : cpu_budget();
@@ -917,12 +994,15 @@ const int32_t* parse_session_display(const ParseSession* s) { return s->res->dis
 const int32_t* parse_session_shards(const ParseSession* s) { return s->res->shard.data(); }
 const mp2vg_stream_headers_t* parse_session_headers(const ParseSession* s) { return &s->res->hdrs; }
 int parse_session_wait(ParseSession* s, int p) { return s->wait(p); }
+// rows of picture p replaced under MP2VG_PARSE_CONCEAL (after parse_session_wait)
+int parse_session_damage(const ParseSession* s, int p) { return (int)s->damage[p].size(); }
 void parse_session_free(ParseSession* s) { delete s; }
 
 // Coefficient words of picture p (after parse_session_wait).
 size_t parse_session_ncoefs(const ParseSession* s, int p) {
     size_t n = 0;
     for (size_t j = s->pic_job_begin[p]; j < s->pic_job_begin[p + 1]; j++) n += s->outs[j].coefs.size();
+    for (const SliceOut& o : s->extra[p]) n += o.coefs.size();
     return n;
 }
 
@@ -932,15 +1012,16 @@ size_t parse_session_ncoefs(const ParseSession* s, int p) {
 void parse_session_append(ParseSession* s, int p, mp2vg_mb_t* mbs_out, uint32_t* coefs_out, uint32_t base) {
     const size_t n = s->mbs_per_pic;
     memcpy(mbs_out, s->mbs_of(p), n * sizeof(mp2vg_mb_t));
-    for (size_t j = s->pic_job_begin[p]; j < s->pic_job_begin[p + 1]; j++) {
-        SliceOut& o = s->outs[j];
+    auto put = [&](SliceOut& o) {
         if (!o.coefs.empty()) memcpy(coefs_out, o.coefs.data(), o.coefs.size() * 4);
         coefs_out += o.coefs.size();
         mp2vg_mb_t* row = mbs_out + (size_t)o.mb_row * s->C.mbw;
         for (int x = 0; x < s->C.mbw; x++) row[x].coef_off += base;
         base += (uint32_t)o.coefs.size();
         CoefVec().swap(o.coefs);
-    }
+    };
+    for (size_t j = s->pic_job_begin[p]; j < s->pic_job_begin[p + 1]; j++) put(s->outs[j]);
+    for (SliceOut& o : s->extra[p]) put(o);
     if (s->window) {
         {
             std::lock_guard<std::mutex> lk(s->mu);
@@ -973,9 +1054,11 @@ extern "C" int mp2vg_parse_es(const uint8_t* buf, uint64_t len, const mp2vg_conf
     const size_t mbs_per_pic = S->mbs_per_pic;
     mp2vg_parsed* res = S->res;
     const Ctx& C = S->C;
-    std::vector<size_t> base(jobs.size() + 1, 0);
-    for (size_t j = 0; j < jobs.size(); j++) base[j + 1] = base[j] + outs[j].coefs.size();
-    const size_t total = base[jobs.size()];
+    // a picture's words: its slices' in stream order, then its concealed missing rows'
+    std::vector<size_t> pic_base(npics + 1, 0);
+    for (int p = 0; p < npics; p++) pic_base[p + 1] = pic_base[p] + parse_session_ncoefs(S.get(), p);
+    const size_t total = pic_base[npics];
+    (void)jobs;
     if (total >= (1ull << 32)) {
         set_error("batch too large");
         return MP2VG_E_INVALID;
@@ -986,13 +1069,16 @@ extern "C" int mp2vg_parse_es(const uint8_t* buf, uint64_t len, const mp2vg_conf
         for (;;) {
             const int p = next_cp.fetch_add(1);
             if (p >= npics) return;
-            for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1]; j++) {
-                SliceOut& o = outs[j];
-                if (!o.coefs.empty()) memcpy(&res->coefs[base[j]], o.coefs.data(), o.coefs.size() * 4);
+            size_t base = pic_base[p];
+            auto put = [&](SliceOut& o) {
+                if (!o.coefs.empty()) memcpy(&res->coefs[base], o.coefs.data(), o.coefs.size() * 4);
                 mp2vg_mb_t* row = res->mbs.data() + mbs_per_pic * p + (size_t)o.mb_row * C.mbw;
-                for (int x = 0; x < C.mbw; x++) row[x].coef_off += (uint32_t)base[j];
+                for (int x = 0; x < C.mbw; x++) row[x].coef_off += (uint32_t)base;
+                base += o.coefs.size();
                 CoefVec().swap(o.coefs);
-            }
+            };
+            for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1]; j++) put(outs[j]);
+            for (SliceOut& o : S->extra[p]) put(o);
         }
     };
     int nthreads = cfg->num_threads > 0 ? cfg->num_threads : cpu_budget();
@@ -1005,6 +1091,7 @@ extern "C" int mp2vg_parse_es(const uint8_t* buf, uint64_t len, const mp2vg_conf
         for (auto& t : th) t.join();
     }
     tp = trace_phase("parse: concatenate", tp);
+    for (int p = 0; p < npics; p++) res->damage.insert(res->damage.end(), S->damage[p].begin(), S->damage[p].end());
     S->res = nullptr;
     *out = res;
     return MP2VG_OK;
@@ -1036,6 +1123,13 @@ extern "C" int mp2vg_parsed_picture_flags(const mp2vg_parsed_t* p, uint32_t* fla
     if (!p->flags.empty()) memcpy(flags, p->flags.data(), p->flags.size() * 4);
     return (int)p->flags.size();
 }
+extern "C" int mp2vg_parsed_damage(const mp2vg_parsed_t* p, mp2vg_damage_t* out, int32_t max, int32_t* n) {
+    if (!p || !n || max < 0 || (max && !out)) return MP2VG_E_INVALID;
+    *n = (int32_t)p->damage.size();
+    for (int32_t i = 0; i < *n && i < max; i++) out[i] = p->damage[i];
+    return MP2VG_OK;
+}
+extern "C" const char* mp2vg_damage_reason_string(int32_t reason) { return sp_reason_text(reason); }
 extern "C" int mp2vg_parsed_stream_headers(const mp2vg_parsed_t* p, mp2vg_stream_headers_t* out) {
     if (!p || !out) return MP2VG_E_INVALID;
     *out = p->hdrs;
@@ -1165,6 +1259,7 @@ extern "C" int mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_confi
         d.intra_vlc_format = (uint8_t)h.intra_vlc_format;
         d.has_fwd = P.fwd >= 0;
         d.has_bwd = P.bwd >= 0;
+        d.has_conceal_ref = C.conceal && P.conceal_ref >= 0;
         S->hdr.push_back(d);
         S->pic_slice.push_back((uint32_t)S->slices.size());
         std::fill(seen.begin(), seen.end(), 0);
@@ -1187,6 +1282,10 @@ extern "C" int mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_confi
         }
         for (int r = 0; r < C.mbh; r++)
             if (!seen[r]) {
+                if (C.conceal) {  // an empty entry at the picture's start code, after the picture's slices
+                    S->slices.push_back({p, r, P.byte_off, P.byte_off});
+                    continue;
+                }
                 set_error(sp_reason_text(SP_R_ROW_UNCOVERED));
                 return MP2VG_E_UNSUPPORTED;
             }
@@ -1256,11 +1355,19 @@ extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32
         ~Free() { free(p); }
     } guard{bs};
     const uint32_t j0 = s->pic_slice[first], j1 = s->pic_slice[first + npics];
+    const bool conceal = (s->cfg.reserved & MP2VG_PARSE_CONCEAL) != 0;
+    std::vector<mp2vg_mb_t> scratch(mbs ? 0 : g.mbw);  // (the counts call conceals into a scratch row)
     std::vector<SpResult> res(j1 - j0);
     auto row_of = [&](const SpSlice& sl) { return mbs + per_pic * (sl.pic - first) + (uint64_t)sl.mb_row * g.mbw; };
     for (uint32_t j = j0; j < j1; j++) {  // count pass
         const SpSlice& sl = s->slices[j];
         const SpPicHdr& h = s->hdr[sl.pic];
+        SpResult& r = res[j - j0];
+        if (conceal && sl.byte_off == sl.byte_end) {  // a missing row: nothing to parse
+            r = SpResult{MP2VG_E_UNSUPPORTED, SP_R_ROW_UNCOVERED, 0, 0, 0, 0};
+            r.ncoef = sp_conceal_row(g, h, sl.mb_row, SpCountOut{mbs ? row_of(sl) : scratch.data()}, r.uses);
+            continue;
+        }
         if (mbs)
             sp_parse_slice(T, g, h, bs, (int64_t)(sl.byte_off - lo), (int64_t)(sl.byte_end - lo), (int64_t)span,
                            sl.mb_row, SpCountOut{row_of(sl)}, res[j - j0]);
@@ -1271,9 +1378,11 @@ extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32
             set_error("mp2vg_scan_parse_host: iteration bound exceeded");
             return MP2VG_E_STATE;
         }
+        if (conceal && r.status != MP2VG_OK && sp_reason_concealed(r.reason))
+            r.ncoef = sp_conceal_row(g, h, sl.mb_row, SpCountOut{mbs ? row_of(sl) : scratch.data()}, r.uses);
     }
     for (uint32_t j = j0; j < j1; j++)  // the first failing slice in stream order
-        if (res[j - j0].status != MP2VG_OK) {
+        if (res[j - j0].status != MP2VG_OK && !(conceal && sp_reason_concealed(res[j - j0].reason))) {
             sp_set_slice_error(s->slices[j].pic, s->slices[j].byte_off, res[j - j0].reason);
             return res[j - j0].status;
         }
@@ -1295,6 +1404,11 @@ extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32
         const SpSlice& sl = s->slices[j];
         SpResult r2;
         const SpEmitOut eo{row_of(sl), coefs + base[j - j0], res[j - j0].ncoef, (uint32_t)base[j - j0]};
+        if (res[j - j0].reason != SP_OK) {  // a concealed row: its rebased coef_off and its DC words
+            uint32_t uses;
+            if (sp_conceal_row(g, s->hdr[sl.pic], sl.mb_row, eo, uses) != res[j - j0].ncoef) return MP2VG_E_STATE;
+            continue;
+        }
         sp_parse_slice(T, g, s->hdr[sl.pic], bs, (int64_t)(sl.byte_off - lo), (int64_t)(sl.byte_end - lo), (int64_t)span,
                        sl.mb_row, eo, r2);
         if (r2.status != MP2VG_OK || r2.ncoef != res[j - j0].ncoef) {

@@ -39,8 +39,12 @@ struct EsState {
     // host sides of the copies (kept here so that they outlive every copy in flight)
     std::vector<uint8_t> h_small;
     std::vector<uint32_t> h_uses;
-    unsigned long long h_summary[2] = {0, 0};
+    unsigned long long h_summary[3] = {0, 0, 0};
     SpResult h_res{};
+    // MP2VG_PARSE_CONCEAL: the per-slice results (read back only when the scan kernel counted
+    // damage) and the rows the last upload replaced (mp2vg_last_upload_damage)
+    std::vector<SpResult> h_all;
+    std::vector<mp2vg_damage_t> damage;
 };
 
 void es_state_free(void* p) {
@@ -103,10 +107,12 @@ int upload_es(mp2vg_ctx_t* c, const mp2vg_scan* scan, const mp2vg_picture_t* pic
         HIPCHK(hipMalloc((void**)&S.d_tables, nw * sizeof(uint32_t)));
         HIPCHK(hipMemcpy(S.d_tables, w, nw * sizeof(uint32_t), hipMemcpyHostToDevice));
         S.T.w = S.d_tables;
-        HIPCHK(hipMalloc((void**)&S.d_summary, 2 * sizeof(unsigned long long)));
+        HIPCHK(hipMalloc((void**)&S.d_summary, 3 * sizeof(unsigned long long)));
         for (hipEvent_t& e : S.ev) HIPCHK(hipEventCreate(&e));
     }
     S.timed = false;
+    S.damage.clear();
+    const bool conceal = (scan->cfg.reserved & MP2VG_PARSE_CONCEAL) != 0;
 
     // the range's bitstream, with kSpanPad zero bytes after it; offsets rebased to the span
     uint64_t lo, hi;
@@ -129,8 +135,10 @@ int upload_es(mp2vg_ctx_t* c, const mp2vg_scan* scan, const mp2vg_picture_t* pic
         DevSlice* sl = (DevSlice*)(S.h_small.data() + o_sl);
         for (uint32_t j = j0; j < j1; j++) {
             const SpSlice& s = scan->slices[j];
-            sl[j - j0] = {(uint32_t)(s.pic - first), (uint32_t)s.mb_row, (uint32_t)(s.byte_off - lo),
-                          (uint32_t)(s.byte_end - lo)};
+            // (a missing row's empty entry sits at its picture's start code, in front of the span)
+            const bool empty = s.byte_off == s.byte_end;
+            sl[j - j0] = {(uint32_t)(s.pic - first), (uint32_t)s.mb_row, empty ? 0u : (uint32_t)(s.byte_off - lo),
+                          empty ? 0u : (uint32_t)(s.byte_end - lo)};
         }
         memcpy(S.h_small.data() + o_hdr, scan->hdr.data() + first, sizeof(SpPicHdr) * npics);
         uint32_t* mbf = (uint32_t*)(S.h_small.data() + o_mbf);
@@ -163,8 +171,10 @@ int upload_es(mp2vg_ctx_t* c, const mp2vg_scan* scan, const mp2vg_picture_t* pic
     a.base = S.d_base;
     a.uses = S.d_uses;
     a.npics = (uint32_t)npics;
+    a.conceal = conceal;
     HIPCHK(hipEventRecord(S.ev[0], st));
     HIPCHK(launch_parse_count(a, st));
+    HIPCHK(launch_parse_conceal(a, st));  // (counted with the count pass in mp2vg_last_parse_times)
     HIPCHK(hipEventRecord(S.ev[1], st));
     HIPCHK(launch_parse_scan(a, (const uint32_t*)(S.d_small + o_ps), S.d_summary, st));
     HIPCHK(hipEventRecord(S.ev[2], st));
@@ -181,6 +191,25 @@ int upload_es(mp2vg_ctx_t* c, const mp2vg_scan* scan, const mp2vg_picture_t* pic
         return S.h_res.status != MP2VG_OK ? S.h_res.status : MP2VG_E_INVALID;
     }
     const uint64_t total = S.h_summary[0];
+    // damage: the slices' results come back, damaged I pictures with a conceal reference are re-typed
+    // in this call's copy of the picture records (the copy es_commit makes resident), and the list
+    // is kept for mp2vg_last_upload_damage.  A clean upload copies nothing more.
+    std::vector<mp2vg_picture_t> retyped;
+    if (conceal && S.h_summary[2]) {
+        S.h_all.resize(ns);
+        HIPCHK(hipMemcpy(S.h_all.data(), S.d_res, sizeof(SpResult) * ns, hipMemcpyDeviceToHost));
+        retyped.assign(pics, pics + npics);
+        for (uint32_t j = 0; j < ns; j++) {
+            const SpResult& r = S.h_all[j];
+            if (r.status == MP2VG_OK) continue;
+            const SpSlice& s = scan->slices[j0 + j];
+            S.damage.push_back({s.pic - first, s.mb_row, r.status, r.reason, s.byte_off});
+        }
+        for (int32_t i = 0; i < npics; i++)  // (bit 2 of the scan kernel's per-picture word: a concealed row)
+            if ((S.h_uses[i] & 4) && retyped[i].picture_coding_type == 1 && scan->hdr[first + i].has_conceal_ref)
+                retyped[i].picture_coding_type = 2;
+        pics = retyped.data();
+    }
     uint32_t* d_coefs = nullptr;
     if (int rc = es_coefs(c, total, &d_coefs)) return rc;
     a.coefs = d_coefs;
@@ -210,6 +239,14 @@ extern "C" int mp2vg_batch_upload_es(mp2vg_ctx_t* c, const mp2vg_scan_t* scan, c
         return MP2VG_E_INVALID;
     }
     return upload_es(c, scan, pics, first, npics);
+}
+
+extern "C" int mp2vg_last_upload_damage(mp2vg_ctx_t* c, mp2vg_damage_t* out, int32_t max, int32_t* n) {
+    if (!c || !n || max < 0 || (max && !out)) return MP2VG_E_INVALID;
+    const EsState* s = (const EsState*)ctx_es_state(c);
+    *n = s ? (int32_t)s->damage.size() : 0;
+    for (int32_t i = 0; i < *n && i < max; i++) out[i] = s->damage[i];
+    return MP2VG_OK;
 }
 
 extern "C" int mp2vg_last_parse_times(mp2vg_ctx_t* c, float ms[3]) {

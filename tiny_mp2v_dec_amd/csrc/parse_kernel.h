@@ -31,11 +31,15 @@ struct ParseArgs {
     uint32_t* base;          // per slice: first word (scan); base[nslices] = total
     uint32_t* uses;          // per picture: bit 0 forward, bit 1 backward (scan)
     uint32_t npics;
+    uint32_t conceal;        // MP2VG_PARSE_CONCEAL: failed slices and missing rows become replacement rows
 };
 
 // workgroup = one wave of 64 lanes, lane = slice
 hipError_t launch_parse_count(const ParseArgs& a, hipStream_t stream);
-// pic_slice[npics + 1]: each picture's slice range; summary[2]: total words, first failing slice
+// MP2VG_PARSE_CONCEAL (a.conceal; otherwise nothing is launched): after the count pass, before the scan
+hipError_t launch_parse_conceal(const ParseArgs& a, hipStream_t stream);
+// pic_slice[npics + 1]: each picture's slice range; summary[3]: total words, first failing slice
+// that is not concealed, concealed slices
 hipError_t launch_parse_scan(const ParseArgs& a, const uint32_t* pic_slice, unsigned long long* summary,
                              hipStream_t stream);
 hipError_t launch_parse_emit(const ParseArgs& a, hipStream_t stream);

@@ -103,7 +103,8 @@ struct SpTables {
 struct SpPicHdr {  // the per-picture device header
     uint8_t pct, f_code[2][2], intra_dc_precision, frame_pred_frame_dct, concealment_motion_vectors,
         q_scale_type, intra_vlc_format, has_fwd, has_bwd;
-    uint8_t reserved[4];
+    uint8_t has_conceal_ref;  // I picture, MP2VG_PARSE_CONCEAL: an earlier anchor exists in decode order
+    uint8_t reserved[3];
 };  // 16 bytes
 
 struct SpSlice {  // slice table entry; byte offsets into the scanned stream (or the uploaded span)
@@ -623,5 +624,48 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
 }
 
 #undef SP_FAIL
+
+// ---- concealment (MP2VG_PARSE_CONCEAL, include/mp2vg.h): the one statement of the rule -------
+// A slice that failed for one of these reasons, or a row no slice covers, is replaced as a whole
+// row.  SP_R_ROW_OUTSIDE and SP_R_TWO_SLICES stay rejections: such a slice names no row of its own.
+SP_HD bool sp_reason_concealed(int reason) {
+    return reason == SP_R_ROW_UNCOVERED || (reason >= SP_R_MB_BEYOND_ROW && reason <= SP_R_ROW_NOT_WHOLE);
+}
+
+// The replacement row of picture h, through an output policy (the parser's: SpCountOut writes the
+// records with coef_off relative to the row, SpEmitOut writes the words and rebases coef_off).
+// Every record of the row is written, so nothing the failed parse left behind survives.  Returns
+// the row's word count; `uses` as SpResult.uses.  Calls out.record(x, .) for x in [0, mbw) and
+// out.word(i, .) for i below the returned count only.
+template <class Out>
+SP_HD uint32_t sp_conceal_row(const SpGeom& G, const SpPicHdr& h, int mb_row, const Out& out, uint32_t& uses) {
+    // the reference the row is copied from: 0 forward, 1 backward, -1 none (grey)
+    int dir = -1;
+    if (h.pct == 2) dir = 0;
+    else if (h.pct == 3) dir = h.has_fwd ? 0 : (h.has_bwd ? 1 : -1);
+    else if (h.has_conceal_ref) dir = 0;
+    uses = dir < 0 ? 0u : 1u << dir;
+    const int16_t grey = (int16_t)((1 << (h.intra_dc_precision + 7)) << (3 - h.intra_dc_precision));
+    uint32_t nw = 0;
+    for (int x = 0; x < G.mbw; x++) {
+        mp2vg_mb_t m;
+        memset(&m, 0, sizeof(m));
+        m.x = (uint16_t)x;
+        m.y = (uint16_t)mb_row;
+        m.qscale = 1;
+        m.coef_off = nw;
+        if (dir >= 0) {
+            m.flags = (uint16_t)(dir == 0 ? MP2VG_MB_FWD : MP2VG_MB_BWD);
+        } else {
+            m.flags = MP2VG_MB_INTRA;
+            m.cbp = (uint16_t)((1u << G.nblocks) - 1);
+            m.ncoef = (uint16_t)G.nblocks;
+            for (int b = 0; b < G.nblocks; b++)
+                out.word(nw++, MP2VG_COEF_PACK(grey, 0, b, MP2VG_COEF_DC | MP2VG_COEF_MBX(x)));
+        }
+        out.record(x, m);
+    }
+    return nw;
+}
 
 }  // namespace mp2vg

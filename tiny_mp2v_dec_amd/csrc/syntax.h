@@ -359,5 +359,6 @@ const int32_t* parse_session_shards(const ParseSession* s);            // npics 
 const mp2vg_stream_headers_t* parse_session_headers(const ParseSession* s);
 int parse_session_wait(ParseSession* s, int p);  // status of picture p once its slices are parsed
 size_t parse_session_ncoefs(const ParseSession* s, int p);  // after parse_session_wait
+int parse_session_damage(const ParseSession* s, int p);     // rows replaced (MP2VG_PARSE_CONCEAL); after the wait
 void parse_session_append(ParseSession* s, int p, mp2vg_mb_t* mbs_out, uint32_t* coefs_out, uint32_t base);
 void parse_session_free(ParseSession* s);

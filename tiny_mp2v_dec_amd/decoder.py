@@ -25,6 +25,10 @@ decoder_config_t(device_parse=True) opts into parsing the slices on the device
 (MP2VG_DECODER_DEVICE_PARSE): decode() only scans the stream on the host and no parse workers
 start; frames, order and lanes are the same.  Measured slower than the host parse at the decoder's
 16-picture chunks (profiles/device_parse/README.md): off by default.
+
+decoder_config_t(conceal=True) opts into concealment (MP2VG_PARSE_CONCEAL, include/mp2vg.h): a
+damaged slice or a missing macroblock row costs that row of that picture instead of failing
+decode(); damage_count() then tells how many rows were replaced.  The stream decodes on one lane.
 """
 import ctypes
 from dataclasses import dataclass
@@ -47,10 +51,12 @@ class decoder_config_t:  # noqa: N801  (reference name)
     device_frames: bool = False
     devices: list = None  # GOP sharding over these devices (None: [device])
     device_parse: bool = False  # MP2VG_DECODER_DEVICE_PARSE: slices parsed on the device, no parse workers
+    conceal: bool = False  # MP2VG_PARSE_CONCEAL: damaged rows are replaced, decode() goes on
 
 
 MP2VG_DECODER_DEVICE_FRAMES = 1  # include/mp2vg.h
 MP2VG_DECODER_DEVICE_PARSE = 4
+MP2VG_PARSE_CONCEAL = 8
 _hip = None
 
 
@@ -181,7 +187,8 @@ class mp2v_decoder_c:  # noqa: N801  (reference name)
                                      config.num_threads, config.reordering, config.device)
         self._device = bool(config.device_frames)
         self._cfg.reserved = ((MP2VG_DECODER_DEVICE_FRAMES if self._device else 0) |
-                              (MP2VG_DECODER_DEVICE_PARSE if config.device_parse else 0))
+                              (MP2VG_DECODER_DEVICE_PARSE if config.device_parse else 0) |
+                              (MP2VG_PARSE_CONCEAL if config.conceal else 0))
         self._error = None
 
         def _cb(user, fptr):
@@ -242,6 +249,10 @@ class mp2v_decoder_c:  # noqa: N801  (reference name)
         v = [ctypes.c_int32() for _ in range(4)]
         lib().mp2vg_decoder_handoff_stats(self._h, *[ctypes.byref(x) for x in v])
         return tuple(x.value for x in v)
+
+    def damage_count(self):
+        """Rows replaced in the last decode() (decoder_config_t(conceal=True); else 0)."""
+        return lib().mp2vg_decoder_damage_count(self._h)
 
     def frames_allocated(self):
         """Frame buffers held by the decoder's frame pools (bounded: the renderer back-pressures

@@ -47,12 +47,43 @@ def check_count(status, what):
     return status
 
 
-class Parsed:
-    """Records of a whole elementary stream (pictures in decode order; slot = decode index)."""
+def _damage_array(call, what):
+    """The structured array (_lib.DAMAGE_DTYPE) of a damage query: a counts call, then the entries."""
+    n = ctypes.c_int32()
+    check(call(None, 0, ctypes.byref(n)), what)
+    out = np.zeros(n.value, _lib.DAMAGE_DTYPE)
+    if n.value:
+        check(call(out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)), what)
+    return out
 
-    def __init__(self, es: bytes, width, height, chroma_format, threads=0, reordering=True):
+
+def damage_reason(reason):
+    """The rejection text of a damage entry's reason code (mp2vg_damage_reason_string)."""
+    return lib().mp2vg_damage_reason_string(int(reason)).decode()
+
+
+def effective_pictures(pics, damage):
+    """Picture records as a conceal=True batch decodes them: a damaged I picture that carries a
+    conceal reference is a P picture from it (what the library makes resident), and every other I
+    picture reads nothing (its fwd_slot, kept for slot lifetimes, is cleared here)."""
+    pics = np.array(pics, PIC_DTYPE)
+    hit = np.zeros(len(pics), bool)
+    hit[np.asarray(damage["pic"], np.int64)] = True
+    i_pic = pics["picture_coding_type"] == 1
+    pics["picture_coding_type"][i_pic & hit & (pics["fwd_slot"] >= 0)] = 2
+    pics["fwd_slot"][pics["picture_coding_type"] == 1] = -1
+    return pics
+
+
+class Parsed:
+    """Records of a whole elementary stream (pictures in decode order; slot = decode index).
+    conceal=True (MP2VG_PARSE_CONCEAL, include/mp2vg.h): damaged slices and missing rows are
+    replaced row by row instead of failing the parse; .damage lists them (_lib.DAMAGE_DTYPE)."""
+
+    def __init__(self, es: bytes, width, height, chroma_format, threads=0, reordering=True, conceal=False):
         self.width, self.height, self.chroma_format = width, height, chroma_format
-        cfg = _lib.make_config(width, height, chroma_format, threads=threads, reordering=reordering)
+        cfg = _lib.make_config(width, height, chroma_format, threads=threads, reordering=reordering,
+                               flags=_lib.MP2VG_PARSE_CONCEAL if conceal else 0)
         buf = np.frombuffer(es, dtype=np.uint8)
         h = ctypes.c_void_p()
         check(lib().mp2vg_parse_es(buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
@@ -78,6 +109,7 @@ class Parsed:
             self.shard = np.array(shard[:n], dtype=np.int32)
             self.headers = _lib.StreamHeaders()
             check(lib().mp2vg_parsed_stream_headers(h, ctypes.byref(self.headers)), "parsed_stream_headers")
+            self.damage = _damage_array(lambda o, m, c: lib().mp2vg_parsed_damage(h, o, m, c), "parsed_damage")
         finally:
             lib().mp2vg_parsed_free(h)
 
@@ -89,11 +121,16 @@ class Parsed:
 class Scan:
     """Host scan of an elementary stream (mp2vg_scan_es): what Parsed holds except the MB records
     and coefficient words, which DeviceContext.upload_es has the device parse from the bitstream
-    (parse_host: the same parser on the CPU).  Keeps the stream's bytes alive."""
+    (parse_host: the same parser on the CPU).  Keeps the stream's bytes alive.  conceal=True
+    (MP2VG_PARSE_CONCEAL): the scan lets missing rows through and carries the flag to parse_host and
+    DeviceContext.upload_es, which replace damaged rows; the damage of an upload is
+    DeviceContext.last_damage()."""
 
-    def __init__(self, es: bytes, width, height, chroma_format, reordering=True):
+    def __init__(self, es: bytes, width, height, chroma_format, reordering=True, conceal=False):
         self.width, self.height, self.chroma_format = width, height, chroma_format
-        cfg = _lib.make_config(width, height, chroma_format, reordering=reordering)
+        self.conceal = bool(conceal)
+        cfg = _lib.make_config(width, height, chroma_format, reordering=reordering,
+                               flags=_lib.MP2VG_PARSE_CONCEAL if conceal else 0)
         self._buf = np.frombuffer(es, dtype=np.uint8)
         self.h = ctypes.c_void_p()
         check(lib().mp2vg_scan_es(self._buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
@@ -291,6 +328,11 @@ class DeviceContext:
         self.batch_pictures = 0
         check(lib().mp2vg_batch_upload_es(self.h, scan.h, ptr, int(first), int(npics)), "batch_upload_es")
         self.batch_pictures = int(npics)
+
+    def last_damage(self):
+        """The rows the last upload_es replaced (mp2vg_last_upload_damage; _lib.DAMAGE_DTYPE, pic
+        relative to the uploaded range): empty for a clean upload or a scan without conceal=True."""
+        return _damage_array(lambda o, m, c: lib().mp2vg_last_upload_damage(self.h, o, m, c), "last_upload_damage")
 
     def download_records(self):
         """(mbs, coefs) of the resident batch, copied from HBM (mp2vg_batch_download_records)."""
@@ -571,8 +613,21 @@ def pixel_aspect(headers):
 stream_pixel_aspect = pixel_aspect  # for functions with a `pixel_aspect` argument
 
 
+def _open_stream(es, width, height, chroma_format, device_parse, conceal):
+    return (Scan if device_parse else Parsed)(es, width, height, chroma_format, conceal=conceal)
+
+
+def _make_resident(ctx, parsed, device_parse):
+    """Upload a Scan (device parse) or a Parsed; returns the damage list of a conceal=True stream."""
+    if device_parse:
+        ctx.upload_es(parsed)
+        return ctx.last_damage()
+    ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+    return parsed.damage
+
+
 def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0,
-               device_parse=False):
+               device_parse=False, conceal=False, return_damage=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one torch.uint8 RGB tensor on cuda:<device>, cropped to the sequence header's
     horizontal_size_value x vertical_size_value when these are set and no larger than the coded
@@ -580,8 +635,10 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
     batch in a context of as many slots as it has pictures; a stream without pictures gives an
     empty tensor, and one of more than 65535 pictures is exported in several calls.
     device_parse=True scans the stream on the host and parses its slices on the device (Scan,
-    DeviceContext.upload_es) instead of uploading host-parsed records; the result is the same."""
-    parsed = (Scan if device_parse else Parsed)(es, width, height, chroma_format)
+    DeviceContext.upload_es) instead of uploading host-parsed records; the result is the same.
+    conceal=True decodes a damaged stream (MP2VG_PARSE_CONCEAL: damaged rows are replaced instead of
+    failing the call); return_damage=True returns (tensor, damage), damage as Parsed.damage."""
+    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     size = (w, h) if 0 < w <= width and 0 < h <= height else None
@@ -590,19 +647,16 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
     exp = _lib.make_export(layout, chroma, matrix, size)
     out = _lib.export_out(None, _lib.export_shape(exp, parsed.npics, width, height), device)
     if not parsed.npics:
-        return out
+        return (out, np.zeros(0, _lib.DAMAGE_DTYPE)) if return_damage else out
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
-        if device_parse:
-            ctx.upload_es(parsed)
-        else:
-            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        damage = _make_resident(ctx, parsed, device_parse)
         ctx.decode()
         for i in range(0, parsed.npics, EXPORT_MAX_FRAMES):  # mp2vg_export_slots takes 65535 per call
             part = parsed.display[i:i + EXPORT_MAX_FRAMES]
             ctx.export_rgb(part, out=out[i:i + len(part)], layout=layout, chroma=chroma, matrix=matrix, size=size,
                            sync=False)
         ctx.synchronize()
-        return out
+        return (out, damage) if return_damage else out
 
 
 def items_plan(width, height, chroma_format, size, crops, flips=None, fields=None, clip_len=1, slots=0, dtype="float16",
@@ -649,7 +703,7 @@ def field_plan(display, flags, fields):
 
 def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
                   layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False, fields=None, fit=None,
-                  pad=(0, 0, 0), pixel_aspect="stream"):
+                  pad=(0, 0, 0), pixel_aspect="stream", conceal=False, return_damage=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
     dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
@@ -670,8 +724,10 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     rectangle picked above) into size with the pad colour around it, "cover" fills size with its
     centre crop, both at the shape the stream is shown at: pixel_aspect="stream" takes the stream's
     own (records.pixel_aspect; a stream whose aspect code gives none raises Mp2vgError, it is not
-    guessed at), a tuple (n, d) overrides it."""
-    parsed = (Scan if device_parse else Parsed)(es, width, height, chroma_format)
+    guessed at), a tuple (n, d) overrides it.
+
+    conceal and return_damage as in decode_rgb."""
+    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     if crop is None and 0 < w <= width and 0 < h <= height:
@@ -689,12 +745,9 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     t = _lib.make_tensor(size, crop, dtype, mean, std, layout, chroma, matrix)
     out = _lib.tensor_out(None, _lib.tensor_shape(t, len(slots)), dtype, device)
     if not parsed.npics:
-        return out
+        return (out, np.zeros(0, _lib.DAMAGE_DTYPE)) if return_damage else out
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
-        if device_parse:
-            ctx.upload_es(parsed)
-        else:
-            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        damage = _make_resident(ctx, parsed, device_parse)
         ctx.decode()
         for i in range(0, len(slots), EXPORT_MAX_FRAMES):  # mp2vg_tensor_slots_fields takes 65535 per call
             part = slots[i:i + EXPORT_MAX_FRAMES]
@@ -702,7 +755,7 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
                               matrix=matrix, out=out[i:i + len(part)], sync=False,
                               fields=None if modes is None else modes[i:i + len(part)], place=place, pad=pad)
         ctx.synchronize()
-        return out
+        return (out, damage) if return_damage else out
 
 
 def motion_bytes(width, height, chroma_format, n):
@@ -759,28 +812,31 @@ def reference_distances(pics, display):
     return np.where(ref >= 0, pos[np.maximum(ref, 0)] - here, 0).astype(np.int32)
 
 
-def decode_motion(es, width, height, chroma_format, parse="device", device=0):
+def decode_motion(es, width, height, chroma_format, parse="device", device=0, conceal=False):
     """The motion field and block activity of a whole elementary stream in display order, with no
     reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
     parse (parse="host": Parsed, upload) the stream, make it resident and export
     (DeviceContext.export_motion).  A dict of mv, info and act (torch tensors on cuda:<device>) and
     dist, numpy int32 (n, 2): the signed display-order distance from each picture to its forward
     and backward reference, 0 where there is none (vectors per frame: mv / dist).  At most 65535
-    pictures."""
+    pictures.  conceal=True (MP2VG_PARSE_CONCEAL) exports a damaged stream, its replaced rows as
+    the records that replace them; the dict then holds 'damage' (as Parsed.damage), and dist follows
+    the pictures as decoded (effective_pictures: a re-typed I picture has a forward reference)."""
     if parse not in ("device", "host"):
         raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
     import torch
     torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
-    parsed = (Scan if parse == "device" else Parsed)(es, width, height, chroma_format)
+    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal)
     if not parsed.npics:
         raise ValueError("the stream has no pictures")
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
-        if parse == "device":
-            ctx.upload_es(parsed)
-        else:
-            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        damage = _make_resident(ctx, parsed, parse == "device")
         mv, info, act = ctx.export_motion(parsed.display)
-    return {"mv": mv, "info": info, "act": act, "dist": reference_distances(parsed.pics, parsed.display)}
+    pics = effective_pictures(parsed.pics, damage) if conceal else parsed.pics
+    out = {"mv": mv, "info": info, "act": act, "dist": reference_distances(pics, parsed.display)}
+    if conceal:
+        out["damage"] = damage
+    return out
 
 
 def residual_bytes(width, height, chroma_format, n, dtype="int16"):
@@ -813,7 +869,7 @@ def residual_host(pics, mbs, coefs, width, height, chroma_format, order=None, dt
 
 
 def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int16", chroma=True, zero_intra=False,
-                    parse="device", device=0):
+                    parse="device", device=0, conceal=False):
     """The coded prediction error of an elementary stream's pictures in display order, with no
     reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
     parse (parse="host": Parsed, upload) the stream, make it resident and export once
@@ -821,24 +877,26 @@ def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int1
     and cr (torch tensors on cuda:<device>, cb and cr None without chroma) and types, numpy int32:
     the picture_coding_type (1 I, 2 P, 3 B) of each exported picture.  Size: a 4:2:0 picture at
     int16 is 2 x 1.5 x W x H bytes (half that at int8), so a long stream is exported in ranges of
-    pictures.  At most 65535 pictures."""
+    pictures.  At most 65535 pictures.  conceal=True (MP2VG_PARSE_CONCEAL) exports a damaged stream:
+    the dict then holds 'damage' (as Parsed.damage), and types are those of the pictures as decoded
+    (a re-typed I picture is 2)."""
     if parse not in ("device", "host"):
         raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
     import torch
     torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
-    parsed = (Scan if parse == "device" else Parsed)(es, width, height, chroma_format)
+    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal)
     if not parsed.npics:
         raise ValueError("the stream has no pictures")
     display = np.asarray(parsed.display, np.int32)
     order = display if pictures is None else display[np.asarray(pictures, np.int64)]
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
-        if parse == "device":
-            ctx.upload_es(parsed)
-        else:
-            ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
+        damage = _make_resident(ctx, parsed, parse == "device")
         y, cb, cr = ctx.export_residual(order, dtype=dtype, chroma=chroma, zero_intra=zero_intra)
-    types = np.asarray(parsed.pics["picture_coding_type"], np.int32)[order]
-    return {"y": y, "cb": cb, "cr": cr, "types": types}
+    pics = effective_pictures(parsed.pics, damage) if conceal else parsed.pics
+    out = {"y": y, "cb": cb, "cr": cr, "types": np.asarray(pics["picture_coding_type"], np.int32)[order]}
+    if conceal:
+        out["damage"] = damage
+    return out
 
 
 def frame_yuv_bytes(planes):

@@ -13,7 +13,8 @@ clock around work that ends in a device synchronise, reported as median [min, ma
       frames and with device frames
 
 There is no threshold: the flag is opt-in either way.  Writes device_parse.json and README.md
-into --out.
+into --out.  --conceal runs every parse under MP2VG_PARSE_CONCEAL (the cost of the flag on an
+undamaged stream, profiles/device_parse/conceal.md); --no-dropin leaves (c) out.
 
     python tools/device_parse_bench.py --out profiles/device_parse        # on an MI355X
     python tools/device_parse_bench.py --from-json profiles/device_parse/device_parse.json   # README.md again
@@ -56,6 +57,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--gops", type=int, default=GOPS)
     ap.add_argument("--from-json", help="render README.md again from a device_parse.json; no GPU needed")
+    ap.add_argument("--conceal", action="store_true", help="parse, scan and decode under MP2VG_PARSE_CONCEAL")
+    ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in decoder runs")
     args = ap.parse_args()
     if args.from_json:
         with open(args.from_json) as fh:
@@ -73,6 +76,7 @@ def main():
     es = first_gops(bench.bench_stream("c2", bench.DEFAULT_GOPS["c2"], 1729), args.gops)
     threads = _lib.lib().mp2vg_cpu_budget()
     ms = lambda t0: (time.perf_counter() - t0) * 1e3  # noqa: E731
+    flag = {"conceal": True} if args.conceal else {}
 
     t = {k: [] for k in ("parsed", "upload", "decode_host", "scan", "upload_es", "decode_dev", "host_total",
                          "dev_total", "pass_count", "pass_scan", "pass_emit", "launch_sum", "batch_span")}
@@ -80,7 +84,7 @@ def main():
     with R.DeviceContext(w, h, cf, slots=args.gops * 12) as ctx:
         for rep in range(-1, args.reps):  # -1: warm-up (allocations, the pool's placement calibration)
             t0 = time.perf_counter()
-            parsed = R.Parsed(es, w, h, cf, threads=threads)
+            parsed = R.Parsed(es, w, h, cf, threads=threads, **flag)
             a = ms(t0)
             t1 = time.perf_counter()
             ctx.upload(parsed.pics, parsed.mbs, parsed.coefs)
@@ -94,7 +98,7 @@ def main():
             del parsed
 
             t0 = time.perf_counter()
-            scan = R.Scan(es, w, h, cf)
+            scan = R.Scan(es, w, h, cf, **flag)
             d = ms(t0)
             t1 = time.perf_counter()
             ctx.upload_es(scan)
@@ -115,7 +119,7 @@ def main():
                 t[k].append(v)
 
     dropin = {}
-    for dev_frames in (False, True):
+    for dev_frames in (() if args.no_dropin else (False, True)):
         for dev_parse in (False, True):
             key = f"{'device' if dev_frames else 'host'}_frames_{'device' if dev_parse else 'host'}_parse"
             frames = [0]
@@ -123,7 +127,8 @@ def main():
             def render(fr):
                 frames[0] += 1
 
-            dec = mp2v_decoder_c(decoder_config_t(w, h, cf, device_frames=dev_frames, device_parse=dev_parse), render)
+            dec = mp2v_decoder_c(decoder_config_t(w, h, cf, device_frames=dev_frames, device_parse=dev_parse, **flag),
+                                 render)
             runs = []
             try:
                 for rep in range(-1, min(args.reps, 3)):
@@ -141,13 +146,14 @@ def main():
         "box": socket.gethostname(), "device": torch.cuda.get_device_name(0), "cpu_budget": threads,
         "stream": {"config": "c2", "gops": args.gops, "pictures": npics, "slices": nslices, "bytes": len(es),
                    "record_bytes": nrec},
-        "reps": args.reps, "launches": nlaunch, "ms": {k: stat(v) for k, v in t.items()}, "dropin": dropin,
+        "reps": args.reps, "conceal": bool(args.conceal), "launches": nlaunch, "ms": {k: stat(v) for k, v in t.items()}, "dropin": dropin,
         "provenance": __import__("tiny_mp2v_dec_amd.build", fromlist=["provenance"]).provenance(),
     }
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "device_parse.json"), "w") as fh:
         json.dump(res, fh, indent=1)
-    write_readme(res, args.out)
+    if dropin:  # (README.md reads all three parts)
+        write_readme(res, args.out)
     m = res["ms"]
     print(json.dumps({"host_total_ms": m["host_total"]["median"], "device_total_ms": m["dev_total"]["median"],
                       "passes_ms": [m["pass_count"]["median"], m["pass_scan"]["median"], m["pass_emit"]["median"]],
