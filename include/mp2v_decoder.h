@@ -96,9 +96,12 @@ public:
     // flags: MP2VG_DECODER_DEVICE_FRAMES hands frames over in HBM (get_planes() then returns
     // device pointers); MP2VG_DECODER_DEVICE_PARSE (= kDeviceParse) parses the slices on the device
     // instead of on host threads; MP2VG_PARSE_CONCEAL (= kConceal) replaces damaged macroblock rows
-    // instead of failing decode() (damage_count()); 0 keeps the reference's host frame_c contract
+    // instead of failing decode() (damage_count()); MP2VG_PARSE_STANDARD (= kStandard) admits streams
+    // as ordinary encoders write them (the standard's matrix rule, intra_vlc_format = 0); 0 keeps
+    // the reference's host frame_c contract
     static constexpr int kDeviceParse = MP2VG_DECODER_DEVICE_PARSE;
     static constexpr int kConceal = MP2VG_PARSE_CONCEAL;
+    static constexpr int kStandard = MP2VG_PARSE_STANDARD;
     mp2v_decoder_c(const decoder_config_t& config, std::function<void(frame_c*)> renderer, int device = 0,
                    int flags = 0) {
         decoder_init(config, renderer, device, flags);

@@ -174,6 +174,33 @@ typedef struct mp2vg_config {
  * multi-device decoder runs it on one lane: output never depends on the lane count.  The damage
  * is reported by mp2vg_parsed_damage / mp2vg_last_upload_damage / mp2vg_decoder_damage_count. */
 #define MP2VG_PARSE_CONCEAL 8
+/* mp2vg_config_t.reserved flag (opt-in), honoured exactly where MP2VG_PARSE_CONCEAL is and free to
+ * combine with it and with MP2VG_DECODER_DEVICE_PARSE: streams as ordinary encoders write them.
+ * Two of the reference's limits go; with the flag clear nothing changes.
+ *   Quantiser matrices as 13818-2 6.3.3 and 6.3.11 define them, in place of "a full
+ *   quant_matrix_extension on every picture".  The parse keeps four matrices in coding order.  At
+ *   the start of a call and at every sequence_header: intra = the header's matrix when it loads
+ *   one, else the default intra matrix of 6.3.11; non_intra = the header's, else 16 everywhere;
+ *   chroma_intra = intra; chroma_non_intra = non_intra.  At every quant_matrix_extension, in its
+ *   field order: a loaded intra also replaces chroma_intra, a loaded non_intra also replaces
+ *   chroma_non_intra, then a loaded chroma matrix replaces just itself.  The state holds for the
+ *   picture the extension belongs to and every later one until the next load or sequence_header;
+ *   a picture's W is that state in the picture's scan order, for all three chroma formats.
+ *   intra_vlc_format = 0, per picture: an intra block reads dct_dc_size and the differential as
+ *   ever and then goes on in table B.14 in its "subsequent coefficient" form ('10' is end of block
+ *   and may follow the DC at once, '11s' is run 0 level +-1; the '1s' code belongs to the first
+ *   coefficient of non-intra blocks only).  Pictures with intra_vlc_format = 1 are untouched.
+ * One limit stays: the kernels dequantise blocks 4 and 5 of 4:2:2 and 4:4:4 macroblocks with the luma
+ * matrices where the standard takes the chroma ones, so a 4:2:2 or 4:4:4 picture
+ * whose state has chroma_intra != intra or chroma_non_intra != non_intra is refused
+ * (MP2VG_E_UNSUPPORTED, "picture N: chroma quantiser matrices differ from the luma ones ...");
+ * every stream that never loads a chroma matrix of its own decodes.
+ * Still refused under the flag: field pictures, dual-prime, concealment motion vectors, more than
+ * one slice per macroblock row and slices that start after column 0, MPEG-1, scalable extensions.
+ * And two pieces of arithmetic stay the reference's, not the standard's: half-pel
+ * prediction in both directions is the cascaded average avg(avg, avg), and the IDCT
+ * is the reference's SSE2 one. */
+#define MP2VG_PARSE_STANDARD 16
 
 typedef struct mp2vg_ctx mp2vg_ctx_t;
 
@@ -778,6 +805,18 @@ int  mp2vg_export_matrix(const mp2vg_stream_headers_t* headers, int32_t* matrix)
  * (dw H) : (dh W) reduced by their gcd (720 x 576 at 16:9 is 64:45).  MP2VG_E_UNSUPPORTED for code
  * 0 and codes 5..15; MP2VG_E_INVALID for a size of 0. */
 int  mp2vg_stream_pixel_aspect(const mp2vg_stream_headers_t* headers, int32_t* par_n, int32_t* par_d);
+
+/* What a config for a stream must hold, from the stream itself (host only, no context): the first
+ * sequence_header and the sequence_extension that follows it.  Writes cfg->chroma_format and the
+ * CODED size: cfg->width = 16 * ceil(h / 16); cfg->height = 16 * ceil(v / 16) when
+ * progressive_sequence is set, else 32 * ceil(v / 32) (13818-2 6.3.3), h and v the 14-bit sizes
+ * (value | extension << 12).  The other cfg fields stay as passed.  *headers (optional) gets those
+ * two headers and a sequence_display_extension that follows them; the display size, pixel aspect
+ * and export matrix come from it as from any mp2vg_stream_headers_t.  MP2VG_E_BITSTREAM when no
+ * sequence_header is found; MP2VG_E_UNSUPPORTED, with a message, for an MPEG-1 stream (no
+ * sequence_extension behind the header) and for a coded size above MP2VG_MAX_DIMENSION; cfg is
+ * written only on MP2VG_OK. */
+int  mp2vg_probe_es(const uint8_t* buf, uint64_t len, mp2vg_config_t* cfg, mp2vg_stream_headers_t* headers);
 
 /* ---- host record emitter -------------------------------------------------------------- */
 typedef struct mp2vg_parsed mp2vg_parsed_t;

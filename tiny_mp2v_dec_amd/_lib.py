@@ -183,6 +183,7 @@ EXPORTS = [
     "mp2vg_motion_bytes", "mp2vg_motion_records", "mp2vg_motion_batch", "mp2vg_last_motion_time",
     "mp2vg_residual_bytes", "mp2vg_residual_records", "mp2vg_residual_batch", "mp2vg_last_residual_time",
     "mp2vg_parsed_damage", "mp2vg_last_upload_damage", "mp2vg_damage_reason_string", "mp2vg_decoder_damage_count",
+    "mp2vg_probe_es",
 ]
 
 _lib = None
@@ -295,6 +296,7 @@ def lib():
         "mp2vg_last_upload_damage": ([VP, VP, I32, P(I32)], ctypes.c_int),
         "mp2vg_damage_reason_string": ([I32], ctypes.c_char_p),
         "mp2vg_decoder_damage_count": ([VP], ctypes.c_int),
+        "mp2vg_probe_es": ([VP, U64, P(Config), P(StreamHeaders)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -314,6 +316,12 @@ def check(status, what):
 MP2VG_DECODER_DEVICE_FRAMES, MP2VG_CTX_ONE_STREAM = 1, 2  # mp2vg_config_t.reserved flags
 MP2VG_DECODER_DEVICE_PARSE = 4  # drop-in decoder: slices parsed on the device (mp2vg_batch_upload_es)
 MP2VG_PARSE_CONCEAL = 8  # parse / scan / drop-in decoder: damaged rows are replaced, not rejected
+MP2VG_PARSE_STANDARD = 16  # the same three: default / sequence-header matrices, intra_vlc_format = 0
+
+
+def parse_flags(conceal=False, standard=False):
+    """mp2vg_config_t.reserved of a parse or scan."""
+    return (MP2VG_PARSE_CONCEAL if conceal else 0) | (MP2VG_PARSE_STANDARD if standard else 0)
 RESIDUAL_DTYPES = {"int16": 0, "int8": 1}  # MP2VG_RESIDUAL_I16 / I8
 RESIDUAL_ZERO_INTRA = 1
 

@@ -16,6 +16,9 @@
 // motion_vector_count 0 for intra macroblocks, mb_decoder.cpp:364-367, so parse_motion_vectors
 // reads two field selects and two vectors, :512-517, where the stream holds one vector, and the
 // parse derails: the reference crashed on the directed stream), scalable extensions.
+// MP2VG_PARSE_STANDARD (include/mp2vg.h) lifts the first two: W comes from the matrix state of
+// 13818-2 6.3.3 / 6.3.11 (MatrixState, kept by pass 1 in coding order), and an intra block of a
+// picture with intra_vlc_format = 0 is read from B.14.  With the flag clear both stay as above.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -50,6 +53,35 @@ struct PictureHdr {
     bool have_qme = false;
     int qme_load[4] = {0, 0, 0, 0};
     uint8_t qme[4][64] = {};
+    uint8_t state[4][64] = {};  // MP2VG_PARSE_STANDARD: the matrices in force after the picture's own extension
+};
+
+// The quantiser matrices in force (13818-2 6.3.3, 6.3.11), in the order the bitstream carries them
+// (zigzag, as build_W expects): [0] intra, [1] non-intra, [2] chroma intra, [3] chroma non-intra.
+struct MatrixState {
+    uint8_t m[4][64];
+    // a sequence_header: its matrices where it loads them (else NULL), the defaults where not
+    void reset(const uint8_t* intra, const uint8_t* non_intra) {
+        // the default intra matrix as 6.3.11 prints it, in raster order
+        static const uint8_t kDefaultIntraRaster[64] = {
+            8,  16, 19, 22, 26, 27, 29, 34, 16, 16, 22, 24, 27, 29, 34, 37, 19, 22, 26, 27, 29, 34,
+            34, 38, 22, 22, 26, 27, 29, 34, 37, 40, 22, 26, 27, 29, 32, 35, 40, 48, 26, 27, 29, 32,
+            35, 40, 48, 58, 26, 27, 29, 34, 38, 46, 56, 69, 27, 29, 35, 38, 46, 56, 69, 83};
+        for (int i = 0; i < 64; i++) {
+            m[0][i] = intra ? intra[i] : kDefaultIntraRaster[kScanRaster[0][i]];
+            m[1][i] = non_intra ? non_intra[i] : 16;
+        }
+        memcpy(m[2], m[0], 64);
+        memcpy(m[3], m[1], 64);
+    }
+    // a quant_matrix_extension, in its field order: a luma load also replaces its chroma matrix
+    void load(const int loaded[4], const uint8_t q[4][64]) {
+        for (int k = 0; k < 4; k++) {
+            if (!loaded[k]) continue;
+            memcpy(m[k], q[k], 64);
+            if (k < 2) memcpy(m[k + 2], q[k], 64);
+        }
+    }
 };
 
 struct SliceJob {
@@ -134,6 +166,7 @@ struct Ctx {
     int width, height, mbw, mbh;
     int vertical_size_value = 0;
     bool conceal = false;     // MP2VG_PARSE_CONCEAL
+    bool standard = false;    // MP2VG_PARSE_STANDARD
     std::vector<PicWork> pics;
     mp2vg_stream_headers_t hdrs{};
 };
@@ -382,9 +415,11 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
         m.coef_off = (uint32_t)out.coefs.size();
 
         // blocks (decode_transform_template / decode_block_template / parse_block)
-        if (intra && h.intra_vlc_format == 0)
+        // (MP2VG_PARSE_STANDARD: such a block goes on in B.14 after its DC, in the table's
+        // "subsequent coefficient" form, which is what T.coefs[0] holds)
+        if (intra && h.intra_vlc_format == 0 && !C.standard)
             FAIL(MP2VG_E_UNSUPPORTED, "intra macroblock with intra_vlc_format=0 (reference mis-parses)");
-        const int tab = intra ? 1 : 0;
+        const int tab = intra && h.intra_vlc_format ? 1 : 0;
         const CoefLut& cf_lut = T.coefs[tab];
         // room for the MB's worst case (64 words per coded block), written through a raw pointer
         const size_t n0 = out.coefs.size();
@@ -659,6 +694,54 @@ struct ParseSession {
     }
 };
 
+// sequence_header / sequence_extension / sequence_display_extension bodies (after the start code,
+// and after the identifier for the extensions): mp2v_hdr.cpp:4-52
+static void read_sequence_header(BitReader& br, mp2vg_sequence_header_t& sh) {
+    sh.sequence_header_code = 0x1B3;
+    sh.horizontal_size_value = br.read(12);
+    sh.vertical_size_value = br.read(12);
+    sh.aspect_ratio_information = br.read(4);
+    sh.frame_rate_code = br.read(4);
+    sh.bit_rate_value = br.read(18);
+    br.skip(1);  // marker_bit
+    sh.vbv_buffer_size_value = br.read(10);
+    sh.constrained_parameters_flag = br.read(1);
+    sh.load_intra_quantiser_matrix = br.read(1);
+    if (sh.load_intra_quantiser_matrix)
+        for (int i = 0; i < 64; i++) sh.intra_quantiser_matrix[i] = (uint8_t)br.read(8);
+    sh.load_non_intra_quantiser_matrix = br.read(1);
+    if (sh.load_non_intra_quantiser_matrix)
+        for (int i = 0; i < 64; i++) sh.non_intra_quantiser_matrix[i] = (uint8_t)br.read(8);
+}
+static void read_sequence_extension(BitReader& br, mp2vg_sequence_extension_t& se) {
+    se.extension_start_code_identifier = 1;
+    se.profile_and_level_indication = br.read(8);
+    se.progressive_sequence = br.read(1);
+    se.chroma_format = br.read(2);
+    se.horizontal_size_extension = br.read(2);
+    se.vertical_size_extension = br.read(2);
+    se.bit_rate_extension = br.read(12);
+    br.skip(1);  // marker_bit
+    se.vbv_buffer_size_extension = br.read(8);
+    se.low_delay = br.read(1);
+    se.frame_rate_extension_n = br.read(2);
+    se.frame_rate_extension_d = br.read(5);
+}
+static void read_sequence_display_extension(BitReader& br, mp2vg_sequence_display_extension_t& de) {
+    de = mp2vg_sequence_display_extension_t{};
+    de.extension_start_code_identifier = 2;
+    de.video_format = br.read(3);
+    de.colour_description = br.read(1);
+    if (de.colour_description) {
+        de.colour_primaries = br.read(8);
+        de.transfer_characteristics = br.read(8);
+        de.matrix_coefficients = br.read(8);
+    }
+    de.display_horizontal_size = br.read(14);
+    br.skip(1);  // marker_bit
+    de.display_vertical_size = br.read(14);
+}
+
 // Pass 1: start codes and headers -> C (geometry, per-picture headers, W, references, slices) and
 // res (picture records, GOP index, stream headers, shards, display order).  Shared by the parse
 // session and mp2vg_scan_es.
@@ -671,6 +754,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
     C.mbh = cfg->height / 16;
     C.g.init(cfg->width, cfg->height, cfg->chroma_format);
     C.conceal = (cfg->reserved & MP2VG_PARSE_CONCEAL) != 0;
+    C.standard = (cfg->reserved & MP2VG_PARSE_STANDARD) != 0;
 
     double tp = now_ms();
     // ---- pass 1: start codes and headers, serially (decoder.cpp:278-329) ----
@@ -702,6 +786,9 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
     bool seq_end = false;
     bool gop_closed = false;
     int gop_anchors = 0;  // anchors decoded since the last group_of_pictures_header
+    // MP2VG_PARSE_STANDARD: the quantiser matrices in force, in coding order (13818-2 6.3.11)
+    MatrixState mat;
+    mat.reset(nullptr, nullptr);
     for (size_t k = 0; k < sc.size() && !seq_end; k++) {
         uint64_t off = sc[k];
         uint64_t end = (k + 1 < sc.size()) ? sc[k + 1] : len;
@@ -710,53 +797,19 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         br.skip(32);
         if (code == 0xB3) {  // sequence_header (mp2v_hdr.cpp:4-21): a later one overwrites
             mp2vg_sequence_header_t& sh = C.hdrs.sequence_header;
-            sh.sequence_header_code = 0x1B3;
-            sh.horizontal_size_value = br.read(12);
-            sh.vertical_size_value = br.read(12);
-            sh.aspect_ratio_information = br.read(4);
-            sh.frame_rate_code = br.read(4);
-            sh.bit_rate_value = br.read(18);
-            br.skip(1);  // marker_bit
-            sh.vbv_buffer_size_value = br.read(10);
-            sh.constrained_parameters_flag = br.read(1);
-            sh.load_intra_quantiser_matrix = br.read(1);
-            if (sh.load_intra_quantiser_matrix)
-                for (int i = 0; i < 64; i++) sh.intra_quantiser_matrix[i] = (uint8_t)br.read(8);
-            sh.load_non_intra_quantiser_matrix = br.read(1);
-            if (sh.load_non_intra_quantiser_matrix)
-                for (int i = 0; i < 64; i++) sh.non_intra_quantiser_matrix[i] = (uint8_t)br.read(8);
+            read_sequence_header(br, sh);
             C.vertical_size_value = (int)sh.vertical_size_value;
+            mat.reset(sh.load_intra_quantiser_matrix ? sh.intra_quantiser_matrix : nullptr,
+                      sh.load_non_intra_quantiser_matrix ? sh.non_intra_quantiser_matrix : nullptr);
         } else if (code == 0xB5) {  // extension (decoder.cpp:202-242)
             int id = (int)br.read(4);
             if (id == 1) {  // sequence_extension (mp2v_hdr.cpp:23-37)
                 mp2vg_sequence_extension_t& se = C.hdrs.sequence_extension;
-                se.extension_start_code_identifier = (uint32_t)id;
-                se.profile_and_level_indication = br.read(8);
-                se.progressive_sequence = br.read(1);
-                se.chroma_format = br.read(2);
-                se.horizontal_size_extension = br.read(2);
-                se.vertical_size_extension = br.read(2);
-                se.bit_rate_extension = br.read(12);
-                br.skip(1);  // marker_bit
-                se.vbv_buffer_size_extension = br.read(8);
-                se.low_delay = br.read(1);
-                se.frame_rate_extension_n = br.read(2);
-                se.frame_rate_extension_d = br.read(5);
+                read_sequence_extension(br, se);
                 seq_chroma = (int)se.chroma_format;
             } else if (id == 2) {  // sequence_display_extension (mp2v_hdr.cpp:39-52)
                 mp2vg_sequence_display_extension_t& de = C.hdrs.sequence_display_extension;
-                de = mp2vg_sequence_display_extension_t{};
-                de.extension_start_code_identifier = (uint32_t)id;
-                de.video_format = br.read(3);
-                de.colour_description = br.read(1);
-                if (de.colour_description) {
-                    de.colour_primaries = br.read(8);
-                    de.transfer_characteristics = br.read(8);
-                    de.matrix_coefficients = br.read(8);
-                }
-                de.display_horizontal_size = br.read(14);
-                br.skip(1);  // marker_bit
-                de.display_vertical_size = br.read(14);
+                read_sequence_display_extension(br, de);
                 C.hdrs.have_sequence_display_extension = 1;
             } else if (id == 5) {
                 set_error("scalable extensions are not supported by the reference path");
@@ -785,6 +838,8 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
                     if (h.qme_load[m])
                         for (int i = 0; i < 64; i++) h.qme[m][i] = (uint8_t)br.read(8);
                 }
+                mat.load(h.qme_load, h.qme);
+                memcpy(h.state, mat.m, sizeof h.state);
             }
         } else if (code == 0xB8) {  // group_of_pictures_header (mp2v_hdr.cpp:77-83)
             gop++;
@@ -802,6 +857,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
             pw.hdr.temporal_reference = (int)br.read(10);
             pw.hdr.pct = (int)br.read(3);
             pw.gop = gop < 0 ? 0 : gop;
+            memcpy(pw.hdr.state, mat.m, sizeof pw.hdr.state);  // (its own extension, if any, comes next)
             if (pw.hdr.pct < 1 || pw.hdr.pct > 3) {
                 set_error("unsupported picture_coding_type");
                 return MP2VG_E_UNSUPPORTED;
@@ -849,11 +905,20 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         }
     }
     // ---- picture-level validation + W (decoder.cpp:154-192) ----
-    for (auto& P : C.pics) {
+    for (size_t pi = 0; pi < C.pics.size(); pi++) {
+        PicWork& P = C.pics[pi];
         PictureHdr& h = P.hdr;
         if (!h.have_pcext) { set_error("MPEG-1 picture (no picture_coding_extension)"); return MP2VG_E_UNSUPPORTED; }
         if (h.picture_structure != 3) { set_error("field pictures"); return MP2VG_E_UNSUPPORTED; }
-        if (!h.have_qme || !(h.qme_load[0] && h.qme_load[1] && h.qme_load[2] && h.qme_load[3])) {
+        if (C.standard) {
+            // blocks 4 and 5 of 4:2:2 and 4:4:4 macroblocks are dequantised with W[0] / W[1],
+            // which is the standard's result only while the chroma matrices equal the luma ones
+            if (C.g.cf != 1 && (memcmp(h.state[2], h.state[0], 64) || memcmp(h.state[3], h.state[1], 64))) {
+                set_error("picture " + std::to_string(pi) + ": chroma quantiser matrices differ from the luma ones in " +
+                          (C.g.cf == 2 ? "4:2:2" : "4:4:4") + " (blocks 4 and 5 are dequantised with the luma matrices)");
+                return MP2VG_E_UNSUPPORTED;
+            }
+        } else if (!h.have_qme || !(h.qme_load[0] && h.qme_load[1] && h.qme_load[2] && h.qme_load[3])) {
             set_error("picture without a full quant_matrix_extension (reference decoder.cpp:185-191)");
             return MP2VG_E_UNSUPPORTED;
         }
@@ -877,7 +942,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
                 }
         }
         if (P.slices.empty()) { set_error("picture without slices"); return MP2VG_E_BITSTREAM; }
-        build_W(h.qme, h.alternate_scan, P.W);
+        build_W(C.standard ? h.state : h.qme, h.alternate_scan, P.W);
     }
     tp = trace_phase("parse: headers", tp);
     const int npics = (int)C.pics.size();
@@ -939,6 +1004,73 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
         }
         if (held >= 0) res->display.push_back(held);
     }
+    return MP2VG_OK;
+}
+
+extern "C" int mp2vg_probe_es(const uint8_t* buf, uint64_t len, mp2vg_config_t* cfg, mp2vg_stream_headers_t* headers) {
+    if (!cfg || (!buf && len)) return MP2VG_E_INVALID;
+    // the start code after position `from` (its first 00), or len
+    auto next_code = [&](uint64_t from) {
+        for (uint64_t k = from; k + 3 < len; k++)
+            if (buf[k] == 0 && buf[k + 1] == 0 && buf[k + 2] == 1) return k;
+        return len;
+    };
+    uint64_t off = next_code(0);
+    while (off < len && buf[off + 3] != 0xB3) off = next_code(off + 3);
+    if (off >= len) {
+        set_error("no sequence_header in the stream");
+        return MP2VG_E_BITSTREAM;
+    }
+    mp2vg_stream_headers_t H{};
+    uint64_t end = next_code(off + 4);
+    {
+        BitReader br(buf + off, buf + end);
+        br.skip(32);
+        read_sequence_header(br, H.sequence_header);
+    }
+    off = end;
+    end = off < len ? next_code(off + 4) : len;
+    bool have_ext = false;
+    if (off < len && buf[off + 3] == 0xB5) {
+        BitReader br(buf + off, buf + end);
+        br.skip(32);
+        if (br.read(4) == 1) {
+            read_sequence_extension(br, H.sequence_extension);
+            have_ext = true;
+        }
+    }
+    if (!have_ext) {
+        set_error("MPEG-1 stream (no sequence_extension after the sequence_header)");
+        return MP2VG_E_UNSUPPORTED;
+    }
+    // extension_and_user_data(0): a sequence_display_extension may follow, user data between
+    for (off = end; off < len && (buf[off + 3] == 0xB5 || buf[off + 3] == 0xB2); off = end) {
+        end = next_code(off + 4);
+        if (buf[off + 3] != 0xB5) continue;
+        BitReader br(buf + off, buf + end);
+        br.skip(32);
+        if (br.read(4) == 2) {
+            read_sequence_display_extension(br, H.sequence_display_extension);
+            H.have_sequence_display_extension = 1;
+        }
+    }
+    const int h = (int)(H.sequence_header.horizontal_size_value | H.sequence_extension.horizontal_size_extension << 12);
+    const int v = (int)(H.sequence_header.vertical_size_value | H.sequence_extension.vertical_size_extension << 12);
+    const int cw = (h + 15) / 16 * 16;
+    const int ch = H.sequence_extension.progressive_sequence ? (v + 15) / 16 * 16 : (v + 31) / 32 * 32;
+    if (cw > MP2VG_MAX_DIMENSION || ch > MP2VG_MAX_DIMENSION || cw < 16 || ch < 16) {
+        set_error("coded size " + std::to_string(cw) + " x " + std::to_string(ch) + " outside 16 .. " +
+                  std::to_string(MP2VG_MAX_DIMENSION) + " (MP2VG_MAX_DIMENSION)");
+        return MP2VG_E_UNSUPPORTED;
+    }
+    if (H.sequence_extension.chroma_format < 1) {
+        set_error("reserved chroma_format 0");
+        return MP2VG_E_UNSUPPORTED;
+    }
+    cfg->width = cw;
+    cfg->height = ch;
+    cfg->chroma_format = (int32_t)H.sequence_extension.chroma_format;
+    if (headers) *headers = H;
     return MP2VG_OK;
 }
 
@@ -1260,6 +1392,7 @@ extern "C" int mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_confi
         d.has_fwd = P.fwd >= 0;
         d.has_bwd = P.bwd >= 0;
         d.has_conceal_ref = C.conceal && P.conceal_ref >= 0;
+        d.intra_tab = (uint8_t)(h.intra_vlc_format ? 1 : C.standard ? 0 : SP_INTRA_TAB_REFUSED);
         S->hdr.push_back(d);
         S->pic_slice.push_back((uint32_t)S->slices.size());
         std::fill(seen.begin(), seen.end(), 0);

@@ -100,12 +100,19 @@ struct SpTables {
     uint32_t mba_val, mbtype_val[4], cbp_val, dc_luma_val, dc_chroma_val, rev6;
 };
 
+enum { SP_INTRA_TAB_REFUSED = 2 };
+
 struct SpPicHdr {  // the per-picture device header
     uint8_t pct, f_code[2][2], intra_dc_precision, frame_pred_frame_dct, concealment_motion_vectors,
         q_scale_type, intra_vlc_format, has_fwd, has_bwd;
     uint8_t has_conceal_ref;  // I picture, MP2VG_PARSE_CONCEAL: an earlier anchor exists in decode order
-    uint8_t reserved[3];
+    // the coefficient table of the picture's intra blocks, filled by the scan: 1 = B.15
+    // (intra_vlc_format 1), 0 = B.14 (intra_vlc_format 0 under MP2VG_PARSE_STANDARD), SP_INTRA_TAB_REFUSED
+    // = intra_vlc_format 0 without the flag.  The one byte the parser reads of the two settings.
+    uint8_t intra_tab;
+    uint8_t reserved[2];
 };  // 16 bytes
+static_assert(sizeof(SpPicHdr) == 16, "SpPicHdr is the 16-byte per-picture device header");
 
 struct SpSlice {  // slice table entry; byte offsets into the scanned stream (or the uploaded span)
     int32_t pic, mb_row;
@@ -536,13 +543,15 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
         m.qscale = (uint8_t)qscale;
         m.coef_off = nw;
         // (the record as the host emitter leaves it when a block fails: ncoef 0)
-        if (intra && h.intra_vlc_format == 0) {
+        // (intra_vlc_format = 0: refused, or under MP2VG_PARSE_STANDARD the block goes on in B.14 after
+        // its DC, in the table's "subsequent coefficient" form, which is what coef1[0] / coef2[0] hold)
+        if (intra && h.intra_tab > 1) {  // SP_INTRA_TAB_REFUSED (any value that names no table)
             out.record(x, m);
             SP_FAIL(MP2VG_E_UNSUPPORTED, SP_R_INTRA_VLC0);
         }
 
         // blocks
-        const int tab = intra ? 1 : 0;
+        const int tab = intra ? h.intra_tab : 0;
         const uint32_t* const lut1 = w + T.coef1[tab];
         const uint32_t* const lut2 = w + T.coef2[tab];
         const uint32_t mbx_tag = MP2VG_COEF_MBX(x);

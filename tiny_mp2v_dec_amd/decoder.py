@@ -29,6 +29,10 @@ start; frames, order and lanes are the same.  Measured slower than the host pars
 decoder_config_t(conceal=True) opts into concealment (MP2VG_PARSE_CONCEAL, include/mp2vg.h): a
 damaged slice or a missing macroblock row costs that row of that picture instead of failing
 decode(); damage_count() then tells how many rows were replaced.  The stream decodes on one lane.
+
+decoder_config_t(standard=True) opts into streams as ordinary encoders write them
+(MP2VG_PARSE_STANDARD, include/mp2vg.h): quantiser matrices from the sequence header, the defaults
+and partial extensions, and intra_vlc_format = 0.
 """
 import ctypes
 from dataclasses import dataclass
@@ -52,11 +56,13 @@ class decoder_config_t:  # noqa: N801  (reference name)
     devices: list = None  # GOP sharding over these devices (None: [device])
     device_parse: bool = False  # MP2VG_DECODER_DEVICE_PARSE: slices parsed on the device, no parse workers
     conceal: bool = False  # MP2VG_PARSE_CONCEAL: damaged rows are replaced, decode() goes on
+    standard: bool = False  # MP2VG_PARSE_STANDARD: the standard's matrix rule, intra_vlc_format = 0
 
 
 MP2VG_DECODER_DEVICE_FRAMES = 1  # include/mp2vg.h
 MP2VG_DECODER_DEVICE_PARSE = 4
 MP2VG_PARSE_CONCEAL = 8
+MP2VG_PARSE_STANDARD = 16
 _hip = None
 
 
@@ -188,7 +194,8 @@ class mp2v_decoder_c:  # noqa: N801  (reference name)
         self._device = bool(config.device_frames)
         self._cfg.reserved = ((MP2VG_DECODER_DEVICE_FRAMES if self._device else 0) |
                               (MP2VG_DECODER_DEVICE_PARSE if config.device_parse else 0) |
-                              (MP2VG_PARSE_CONCEAL if config.conceal else 0))
+                              (MP2VG_PARSE_CONCEAL if config.conceal else 0) |
+                              (MP2VG_PARSE_STANDARD if config.standard else 0))
         self._error = None
 
         def _cb(user, fptr):

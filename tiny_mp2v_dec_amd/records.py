@@ -78,12 +78,15 @@ def effective_pictures(pics, damage):
 class Parsed:
     """Records of a whole elementary stream (pictures in decode order; slot = decode index).
     conceal=True (MP2VG_PARSE_CONCEAL, include/mp2vg.h): damaged slices and missing rows are
-    replaced row by row instead of failing the parse; .damage lists them (_lib.DAMAGE_DTYPE)."""
+    replaced row by row instead of failing the parse; .damage lists them (_lib.DAMAGE_DTYPE).
+    standard=True (MP2VG_PARSE_STANDARD): quantiser matrices from the sequence header, the
+    defaults and partial extensions as the standard rules them, and intra_vlc_format = 0."""
 
-    def __init__(self, es: bytes, width, height, chroma_format, threads=0, reordering=True, conceal=False):
+    def __init__(self, es: bytes, width, height, chroma_format, threads=0, reordering=True, conceal=False,
+                 standard=False):
         self.width, self.height, self.chroma_format = width, height, chroma_format
         cfg = _lib.make_config(width, height, chroma_format, threads=threads, reordering=reordering,
-                               flags=_lib.MP2VG_PARSE_CONCEAL if conceal else 0)
+                               flags=_lib.parse_flags(conceal, standard))
         buf = np.frombuffer(es, dtype=np.uint8)
         h = ctypes.c_void_p()
         check(lib().mp2vg_parse_es(buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
@@ -124,13 +127,15 @@ class Scan:
     (parse_host: the same parser on the CPU).  Keeps the stream's bytes alive.  conceal=True
     (MP2VG_PARSE_CONCEAL): the scan lets missing rows through and carries the flag to parse_host and
     DeviceContext.upload_es, which replace damaged rows; the damage of an upload is
-    DeviceContext.last_damage()."""
+    DeviceContext.last_damage().  standard=True (MP2VG_PARSE_STANDARD) as for Parsed; the scan
+    carries it to parse_host and DeviceContext.upload_es too."""
 
-    def __init__(self, es: bytes, width, height, chroma_format, reordering=True, conceal=False):
+    def __init__(self, es: bytes, width, height, chroma_format, reordering=True, conceal=False, standard=False):
         self.width, self.height, self.chroma_format = width, height, chroma_format
         self.conceal = bool(conceal)
+        self.standard = bool(standard)
         cfg = _lib.make_config(width, height, chroma_format, reordering=reordering,
-                               flags=_lib.MP2VG_PARSE_CONCEAL if conceal else 0)
+                               flags=_lib.parse_flags(conceal, standard))
         self._buf = np.frombuffer(es, dtype=np.uint8)
         self.h = ctypes.c_void_p()
         check(lib().mp2vg_scan_es(self._buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
@@ -613,8 +618,25 @@ def pixel_aspect(headers):
 stream_pixel_aspect = pixel_aspect  # for functions with a `pixel_aspect` argument
 
 
-def _open_stream(es, width, height, chroma_format, device_parse, conceal):
-    return (Scan if device_parse else Parsed)(es, width, height, chroma_format, conceal=conceal)
+def _open_stream(es, width, height, chroma_format, device_parse, conceal, standard=False):
+    return (Scan if device_parse else Parsed)(es, width, height, chroma_format, conceal=conceal, standard=standard)
+
+
+def probe(es):
+    """What a stream says about itself before anything is parsed (mp2vg_probe_es): a dict with the
+    coded `width` and `height` and the `chroma_format` every other entry point asks for, the
+    `display_width` and `display_height` (the 14-bit horizontal_size and vertical_size) and the
+    stream `headers` (_lib.StreamHeaders: sequence header, sequence extension and, when one
+    follows them, the sequence display extension).  Mp2vgError for an MPEG-1 stream, a size outside
+    the limits, or a buffer without a sequence header."""
+    buf = np.frombuffer(es, dtype=np.uint8)
+    cfg, hd = _lib.make_config(0, 0, 0), _lib.StreamHeaders()
+    check(lib().mp2vg_probe_es(buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg), ctypes.byref(hd)),
+          "probe_es")
+    sh, se = hd.sequence_header, hd.sequence_extension
+    return {"width": cfg.width, "height": cfg.height, "chroma_format": cfg.chroma_format,
+            "display_width": int(sh.horizontal_size_value | se.horizontal_size_extension << 12),
+            "display_height": int(sh.vertical_size_value | se.vertical_size_extension << 12), "headers": hd}
 
 
 def _make_resident(ctx, parsed, device_parse):
@@ -627,7 +649,7 @@ def _make_resident(ctx, parsed, device_parse):
 
 
 def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0,
-               device_parse=False, conceal=False, return_damage=False):
+               device_parse=False, conceal=False, return_damage=False, standard=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one torch.uint8 RGB tensor on cuda:<device>, cropped to the sequence header's
     horizontal_size_value x vertical_size_value when these are set and no larger than the coded
@@ -637,8 +659,9 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
     device_parse=True scans the stream on the host and parses its slices on the device (Scan,
     DeviceContext.upload_es) instead of uploading host-parsed records; the result is the same.
     conceal=True decodes a damaged stream (MP2VG_PARSE_CONCEAL: damaged rows are replaced instead of
-    failing the call); return_damage=True returns (tensor, damage), damage as Parsed.damage."""
-    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal)
+    failing the call); return_damage=True returns (tensor, damage), damage as Parsed.damage.
+    standard=True (MP2VG_PARSE_STANDARD) admits streams of ordinary encoders, as for Parsed."""
+    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal, standard)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     size = (w, h) if 0 < w <= width and 0 < h <= height else None
@@ -703,7 +726,7 @@ def field_plan(display, flags, fields):
 
 def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
                   layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False, fields=None, fit=None,
-                  pad=(0, 0, 0), pixel_aspect="stream", conceal=False, return_damage=False):
+                  pad=(0, 0, 0), pixel_aspect="stream", conceal=False, return_damage=False, standard=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
     dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
@@ -726,8 +749,8 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     own (records.pixel_aspect; a stream whose aspect code gives none raises Mp2vgError, it is not
     guessed at), a tuple (n, d) overrides it.
 
-    conceal and return_damage as in decode_rgb."""
-    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal)
+    conceal, return_damage and standard as in decode_rgb."""
+    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal, standard)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     if crop is None and 0 < w <= width and 0 < h <= height:
@@ -812,7 +835,7 @@ def reference_distances(pics, display):
     return np.where(ref >= 0, pos[np.maximum(ref, 0)] - here, 0).astype(np.int32)
 
 
-def decode_motion(es, width, height, chroma_format, parse="device", device=0, conceal=False):
+def decode_motion(es, width, height, chroma_format, parse="device", device=0, conceal=False, standard=False):
     """The motion field and block activity of a whole elementary stream in display order, with no
     reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
     parse (parse="host": Parsed, upload) the stream, make it resident and export
@@ -826,7 +849,7 @@ def decode_motion(es, width, height, chroma_format, parse="device", device=0, co
         raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
     import torch
     torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
-    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal)
+    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal, standard)
     if not parsed.npics:
         raise ValueError("the stream has no pictures")
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
@@ -869,7 +892,7 @@ def residual_host(pics, mbs, coefs, width, height, chroma_format, order=None, dt
 
 
 def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int16", chroma=True, zero_intra=False,
-                    parse="device", device=0, conceal=False):
+                    parse="device", device=0, conceal=False, standard=False):
     """The coded prediction error of an elementary stream's pictures in display order, with no
     reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
     parse (parse="host": Parsed, upload) the stream, make it resident and export once
@@ -884,7 +907,7 @@ def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int1
         raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
     import torch
     torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
-    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal)
+    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal, standard)
     if not parsed.npics:
         raise ValueError("the stream has no pictures")
     display = np.asarray(parsed.display, np.int32)

@@ -14,7 +14,9 @@ clock around work that ends in a device synchronise, reported as median [min, ma
 
 There is no threshold: the flag is opt-in either way.  Writes device_parse.json and README.md
 into --out.  --conceal runs every parse under MP2VG_PARSE_CONCEAL (the cost of the flag on an
-undamaged stream, profiles/device_parse/conceal.md); --no-dropin leaves (c) out.
+undamaged stream, profiles/device_parse/conceal.md), --standard under MP2VG_PARSE_STANDARD
+(profiles/device_parse/standard.md; the c2 stream carries full extensions and intra_vlc_format 1, so
+the flag changes none of its records); --no-dropin leaves (c) out.
 
     python tools/device_parse_bench.py --out profiles/device_parse        # on an MI355X
     python tools/device_parse_bench.py --from-json profiles/device_parse/device_parse.json   # README.md again
@@ -58,6 +60,7 @@ def main():
     ap.add_argument("--gops", type=int, default=GOPS)
     ap.add_argument("--from-json", help="render README.md again from a device_parse.json; no GPU needed")
     ap.add_argument("--conceal", action="store_true", help="parse, scan and decode under MP2VG_PARSE_CONCEAL")
+    ap.add_argument("--standard", action="store_true", help="parse, scan and decode under MP2VG_PARSE_STANDARD")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in decoder runs")
     args = ap.parse_args()
     if args.from_json:
@@ -77,6 +80,8 @@ def main():
     threads = _lib.lib().mp2vg_cpu_budget()
     ms = lambda t0: (time.perf_counter() - t0) * 1e3  # noqa: E731
     flag = {"conceal": True} if args.conceal else {}
+    if args.standard:
+        flag["standard"] = True
 
     t = {k: [] for k in ("parsed", "upload", "decode_host", "scan", "upload_es", "decode_dev", "host_total",
                          "dev_total", "pass_count", "pass_scan", "pass_emit", "launch_sum", "batch_span")}
@@ -146,7 +151,7 @@ def main():
         "box": socket.gethostname(), "device": torch.cuda.get_device_name(0), "cpu_budget": threads,
         "stream": {"config": "c2", "gops": args.gops, "pictures": npics, "slices": nslices, "bytes": len(es),
                    "record_bytes": nrec},
-        "reps": args.reps, "conceal": bool(args.conceal), "launches": nlaunch, "ms": {k: stat(v) for k, v in t.items()}, "dropin": dropin,
+        "reps": args.reps, "conceal": bool(args.conceal), "standard": bool(args.standard), "launches": nlaunch, "ms": {k: stat(v) for k, v in t.items()}, "dropin": dropin,
         "provenance": __import__("tiny_mp2v_dec_amd.build", fromlist=["provenance"]).provenance(),
     }
     os.makedirs(args.out, exist_ok=True)
