@@ -102,6 +102,7 @@ public:
     static constexpr int kDeviceParse = MP2VG_DECODER_DEVICE_PARSE;
     static constexpr int kConceal = MP2VG_PARSE_CONCEAL;
     static constexpr int kStandard = MP2VG_PARSE_STANDARD;
+    static constexpr int kSlices = MP2VG_PARSE_SLICES;  // any number of slices per macroblock row
     mp2v_decoder_c(const decoder_config_t& config, std::function<void(frame_c*)> renderer, int device = 0,
                    int flags = 0) {
         decoder_init(config, renderer, device, flags);

@@ -168,8 +168,9 @@ typedef struct mp2vg_config {
  * Always qscale 1, reserved 0, coef_off the running word offset.  A concealed missing row's words
  * follow those of the picture's slices (rows ascending).  Still rejected under the flag: every
  * picture-level and stream-level fault of pass 1 (a picture without any slice among them), "slice
- * row outside the picture", "two slices in one macroblock row", and MP2VG_E_INVALID slice-table
- * entries.  With the flag every anchor but the first depends on the one before it, so the stream
+ * row outside the picture", "two slices in one macroblock row" (without MP2VG_PARSE_SLICES: any
+ * second slice of a row; with it: a slice whose row was seen earlier in the picture but not
+ * immediately before it), and MP2VG_E_INVALID slice-table entries.  With the flag every anchor but the first depends on the one before it, so the stream
  * is one shard (mp2vg_parsed_shards returns 1 whenever an I picture has a conceal reference) and a
  * multi-device decoder runs it on one lane: output never depends on the lane count.  The damage
  * is reported by mp2vg_parsed_damage / mp2vg_last_upload_damage / mp2vg_decoder_damage_count. */
@@ -195,12 +196,42 @@ typedef struct mp2vg_config {
  * whose state has chroma_intra != intra or chroma_non_intra != non_intra is refused
  * (MP2VG_E_UNSUPPORTED, "picture N: chroma quantiser matrices differ from the luma ones ...");
  * every stream that never loads a chroma matrix of its own decodes.
- * Still refused under the flag: field pictures, dual-prime, concealment motion vectors, more than
- * one slice per macroblock row and slices that start after column 0, MPEG-1, scalable extensions.
+ * Still refused under the flag: field pictures, dual-prime, concealment motion vectors, MPEG-1,
+ * scalable extensions, and (unless MP2VG_PARSE_SLICES is set too) more than one slice per macroblock
+ * row and slices that start after column 0.
  * And two pieces of arithmetic stay the reference's, not the standard's: half-pel
  * prediction in both directions is the cascaded average avg(avg, avg), and the IDCT
  * is the reference's SSE2 one. */
 #define MP2VG_PARSE_STANDARD 16
+/* mp2vg_config_t.reserved flag (opt-in), honoured exactly where MP2VG_PARSE_CONCEAL and
+ * MP2VG_PARSE_STANDARD are and free to combine with both and with MP2VG_DECODER_DEVICE_PARSE: any
+ * number of slices per macroblock row, as 13818-2 allows.  With the flag clear nothing changes.
+ * One statement of the rule (csrc/slice_parse.h):
+ *   start   a slice's first macroblock_address_increment (escapes included) names its start column
+ *           x0 = increment - 1.  It is no skip run: no records are written for it, it is legal in
+ *           an I picture, and predictors and quantiser scale start from the slice header as ever.
+ *           x0 >= mb_width is "macroblock beyond the end of the row".
+ *   end     the slice ends at the column x1 where its macroblock loop ends; "slice does not start at
+ *           column 0" and "slice does not cover the whole macroblock row" are not produced.
+ *   scan    a slice whose row is the row of the slice immediately before it in the picture continues
+ *           that row; a slice whose row was seen earlier but not immediately before is still "two
+ *           slices in one macroblock row" (also under MP2VG_PARSE_CONCEAL: it names no row of its own),
+ *           and is reported before any other fault of its picture's slices.
+ *   cover   a row's slices, in stream order, must tile [0, mb_width): the first x0 = 0, each next
+ *           x0 = the previous x1, the last x1 = mb_width.  The row breaks at its first slice that
+ *           failed its parse, that starts past the expected column ("slices of a macroblock row
+ *           leave a gap") or before it ("slices of a macroblock row overlap or are out of order"); a
+ *           row that ends short breaks at its last slice (gap).  Both are MP2VG_E_UNSUPPORTED, and
+ *           the call reports the failing slice that comes first in the stream, whatever its fault:
+ *           "picture N slice @offset: text".
+ * Records stay one per macroblock in raster order and the coefficient words stay the slices' words
+ * in stream order, which on a valid row is raster order: nothing below the parse sees the flag.
+ * With MP2VG_PARSE_CONCEAL concealment stays row-granular: a row that breaks for a concealable reason
+ * (the two above included) is replaced as a whole, its words in the place of its first slice's; the
+ * damage is reported once per row with the blamed slice's status, reason and offset.
+ * Still refused: field pictures, dual-prime, concealment motion vectors, MPEG-1, scalable
+ * extensions, and what MP2VG_PARSE_STANDARD lifts unless that flag is set too. */
+#define MP2VG_PARSE_SLICES 32
 
 typedef struct mp2vg_ctx mp2vg_ctx_t;
 

@@ -317,11 +317,13 @@ MP2VG_DECODER_DEVICE_FRAMES, MP2VG_CTX_ONE_STREAM = 1, 2  # mp2vg_config_t.reser
 MP2VG_DECODER_DEVICE_PARSE = 4  # drop-in decoder: slices parsed on the device (mp2vg_batch_upload_es)
 MP2VG_PARSE_CONCEAL = 8  # parse / scan / drop-in decoder: damaged rows are replaced, not rejected
 MP2VG_PARSE_STANDARD = 16  # the same three: default / sequence-header matrices, intra_vlc_format = 0
+MP2VG_PARSE_SLICES = 32  # the same three: any number of slices per macroblock row
 
 
-def parse_flags(conceal=False, standard=False):
+def parse_flags(conceal=False, standard=False, slices=False):
     """mp2vg_config_t.reserved of a parse or scan."""
-    return (MP2VG_PARSE_CONCEAL if conceal else 0) | (MP2VG_PARSE_STANDARD if standard else 0)
+    return ((MP2VG_PARSE_CONCEAL if conceal else 0) | (MP2VG_PARSE_STANDARD if standard else 0) |
+            (MP2VG_PARSE_SLICES if slices else 0))
 RESIDUAL_DTYPES = {"int16": 0, "int8": 1}  # MP2VG_RESIDUAL_I16 / I8
 RESIDUAL_ZERO_INTRA = 1
 

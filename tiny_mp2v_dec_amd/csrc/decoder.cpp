@@ -250,7 +250,7 @@ extern "C" int mp2vg_decoder_create_multi(const mp2vg_config_t* cfg, const int32
     if (!cfg || !fn || !out || !devices || ndevices < 1 || ndevices > 64) return MP2VG_E_INVALID;
     *out = nullptr;
     if (cfg->reserved & ~(MP2VG_DECODER_DEVICE_FRAMES | MP2VG_DECODER_DEVICE_PARSE | MP2VG_PARSE_CONCEAL |
-                          MP2VG_PARSE_STANDARD)) {
+                          MP2VG_PARSE_STANDARD | MP2VG_PARSE_SLICES)) {
         set_error("unknown decoder flags in mp2vg_config_t.reserved");
         return MP2VG_E_INVALID;
     }

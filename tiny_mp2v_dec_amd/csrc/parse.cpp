@@ -19,6 +19,8 @@
 // MP2VG_PARSE_STANDARD (include/mp2vg.h) lifts the first two: W comes from the matrix state of
 // 13818-2 6.3.3 / 6.3.11 (MatrixState, kept by pass 1 in coding order), and an intra block of a
 // picture with intra_vlc_format = 0 is read from B.14.  With the flag clear both stay as above.
+// MP2VG_PARSE_SLICES lifts "slices not starting at column 0" and "one slice per row": the rule is
+// stated in slice_parse.h (sp_parse_slice, sp_cover_row) and restated here (parse_slice, cover_rows).
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -88,6 +90,10 @@ struct SliceJob {
     int pic;                  // decode index
     uint64_t byte_off;        // offset of the slice start code
     uint64_t byte_end;        // end of the slice payload (next start code)
+    // MP2VG_PARSE_SLICES (parse_session_start): the row the start code names (-1: outside the
+    // picture), and whether that row was seen earlier in the picture but not immediately before
+    int row = -1;
+    bool two = false;
 };
 
 struct PicWork {
@@ -157,6 +163,7 @@ struct SliceOut {
     int status = MP2VG_OK;
     std::string err;
     bool concealed = false;   // MP2VG_PARSE_CONCEAL: the row was replaced (status and err say why)
+    int x0 = 0, x1 = 0;       // the records whose coef_off is relative to coefs: columns [x0, x1) of the row
 };
 
 struct Ctx {
@@ -167,6 +174,7 @@ struct Ctx {
     int vertical_size_value = 0;
     bool conceal = false;     // MP2VG_PARSE_CONCEAL
     bool standard = false;    // MP2VG_PARSE_STANDARD
+    bool slices = false;      // MP2VG_PARSE_SLICES
     std::vector<PicWork> pics;
     mp2vg_stream_headers_t hdrs{};
 };
@@ -214,7 +222,10 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
     br.skip(1);
     if (mb_row < 0 || mb_row >= C.mbh) FAIL(MP2VG_E_UNSUPPORTED, "slice row outside the picture");
     // slices of one picture run on several workers: the row is claimed atomically
-    if (row_done[mb_row].exchange(1, std::memory_order_relaxed)) FAIL(MP2VG_E_UNSUPPORTED, "two slices in one macroblock row");
+    // (MP2VG_PARSE_SLICES: a row has any number of consecutive slices; parse_session_start marked the
+    // rows that have one and the slices that come back to a row left earlier)
+    if (C.slices ? job.two : row_done[mb_row].exchange(1, std::memory_order_relaxed))
+        FAIL(MP2VG_E_UNSUPPORTED, "two slices in one macroblock row");
     out.mb_row = mb_row;
 
     // cache setup (decoder.cpp:125-145)
@@ -226,6 +237,7 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
     uint32_t previous_mb_type = 0;
     mp2vg_mb_t* row = row_base_all + (size_t)mb_row * C.mbw;
     int x = 0;
+    bool first = C.slices;  // MP2VG_PARSE_SLICES: the start column is still to come
     const int pstruct_frame = 1;  // only frame pictures are accepted
     (void)pstruct_frame;
 
@@ -266,7 +278,14 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
         int e = T.mba.decode(br);
         if (e < 0 || e >= 33) FAIL(MP2VG_E_BITSTREAM, "bad macroblock_address_increment");
         inc += kMbaCodes[e].a;
-        if (x == 0 && inc != 1) FAIL(MP2VG_E_UNSUPPORTED, "slice does not start at column 0");
+        if (first) {  // the slice's first increment is its start column, not a skip run
+            if ((uint32_t)(inc - 1) >= (uint32_t)C.mbw) FAIL(MP2VG_E_BITSTREAM, "macroblock beyond the end of the row");
+            x = out.x0 = out.x1 = inc - 1;
+            inc = 1;
+            first = false;
+        } else if (x == 0 && inc != 1) {
+            FAIL(MP2VG_E_UNSUPPORTED, "slice does not start at column 0");
+        }
         // skipped macroblocks (mb_decoder.cpp:541-550)
         if (inc > 1) {
             if (pct == 1) FAIL(MP2VG_E_UNSUPPORTED, "skipped macroblock in an I picture");
@@ -493,8 +512,9 @@ void parse_slice(const Ctx& C, const PicWork& P, const SliceJob& job, mp2vg_mb_t
         if (br.overrun()) FAIL(MP2VG_E_BITSTREAM, "slice overruns the buffer");
         previous_mb_type = mbt;
         x++;
+        out.x1 = x;
     } while (br.peek(23) != 0);
-    if (x != C.mbw) FAIL(MP2VG_E_UNSUPPORTED, "slice does not cover the whole macroblock row");
+    if (x != C.mbw && !C.slices) FAIL(MP2VG_E_UNSUPPORTED, "slice does not cover the whole macroblock row");
 }
 
 #undef FAIL
@@ -517,6 +537,15 @@ struct ParsedImpl {
 }  // namespace mp2vg
 
 struct mp2vg_parsed : mp2vg::ParsedImpl {};
+
+// The macroblock row a slice's start code names: slice_vertical_position, the start code's last
+// byte, extended by the 3 bits after it in pictures taller than 2800 lines (bytes past the buffer
+// read as 0).  May lie outside the picture.
+static int slice_row_of(const uint8_t* buf, uint64_t len, uint64_t off, bool vext) {
+    const int vpos = buf[off + 3];
+    const int ext = vext && off + 4 < len ? buf[off + 4] >> 5 : 0;
+    return (ext << 7) + vpos - 1;
+}
 
 using namespace mp2vg;
 
@@ -622,21 +651,70 @@ struct ParseSession {
         uint32_t uses;
         o.coefs.n = sp_conceal_row(g, h, row, Out{mbs_of(p) + (size_t)row * C.mbw, o.coefs.data()}, uses);
         o.mb_row = row;
+        o.x0 = 0;
+        o.x1 = C.mbw;
         o.concealed = true;
         damage[p].push_back({p, row, status_, reason, byte_off});
         return true;
     }
     static int reason_of(const std::string& text) {
-        for (int r = SP_R_MB_BEYOND_ROW; r <= SP_R_ROW_NOT_WHOLE; r++)
+        for (int r = SP_R_MB_BEYOND_ROW; r <= SP_R_ROW_OVERLAP; r++)
             if (text == sp_reason_text(r)) return r;
         return SP_OK;
+    }
+    // MP2VG_PARSE_SLICES: the cover rule (sp_cover_row, slice_parse.h, restated) on every row of
+    // picture p.  A row's slices are consecutive jobs; they must tile [0, mbw).  The row breaks at its
+    // first slice that failed, starts past the expected column (gap) or before it (overlap), or, when
+    // all fit but end short, at its last slice (gap).  Without concealment the blamed slice carries
+    // the failure; with it the row is replaced, its words in the place of its first slice's, the
+    // other slices of the row keep none.  false: out of memory.
+    bool cover_rows(int p) {
+        const size_t jb = pic_job_begin[p], je = pic_job_begin[p + 1];
+        for (size_t a = jb, b; a < je; a = b) {
+            b = a + 1;
+            if (jobs[a].row < 0 || jobs[a].two) continue;  // (names no row of its own: rejected as it is)
+            while (b < je && jobs[b].row == jobs[a].row && !jobs[b].two) b++;
+            size_t blame = b;
+            int st = MP2VG_OK, why = SP_OK, expect = 0;
+            for (size_t k = a; k < b; k++) {
+                const SliceOut& o = outs[k];
+                if (o.status != MP2VG_OK) {
+                    blame = k, st = o.status, why = reason_of(o.err);
+                    break;
+                }
+                if (o.x0 != expect) {
+                    blame = k, st = MP2VG_E_UNSUPPORTED, why = o.x0 > expect ? SP_R_ROW_GAP : SP_R_ROW_OVERLAP;
+                    break;
+                }
+                expect = o.x1;
+            }
+            if (blame == b) {
+                if (expect == C.mbw) continue;
+                blame = b - 1, st = MP2VG_E_UNSUPPORTED, why = SP_R_ROW_GAP;
+            }
+            if (!(C.conceal && why != SP_OK)) {  // (why == SP_OK: a failure that is no slice-level reason)
+                if (outs[blame].status == MP2VG_OK) outs[blame].status = st, outs[blame].err = sp_reason_text(why);
+                continue;
+            }
+            for (size_t k = a + 1; k < b; k++) {
+                outs[k].status = MP2VG_OK;
+                outs[k].err.clear();
+                outs[k].coefs.n = 0;
+                outs[k].x0 = outs[k].x1 = 0;
+                outs[k].mb_row = jobs[a].row;
+            }
+            outs[a].status = st;
+            outs[a].err = sp_reason_text(why);
+            if (!conceal_row(p, jobs[a].row, st, why, jobs[blame].byte_off, outs[a])) return false;
+        }
+        return true;
     }
     void finish_picture(int p) {
         int st = MP2VG_OK;
         std::string msg;
+        bool nomem = C.slices && !cover_rows(p);
         if (C.conceal) {  // every slice-level rejection becomes a replacement row, then the missing rows
-            bool nomem = false;
-            for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1] && !nomem; j++) {
+            for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1] && !nomem && !C.slices; j++) {
                 SliceOut& o = outs[j];
                 const int why = o.status != MP2VG_OK ? reason_of(o.err) : SP_OK;
                 if (why != SP_OK) nomem = !conceal_row(p, o.mb_row, o.status, why, jobs[j].byte_off, o);
@@ -663,8 +741,11 @@ struct ParseSession {
                 }
             }
         }
+        // (MP2VG_PARSE_SLICES: a slice that comes back to a row left earlier goes first, as in the scan,
+        // which meets it before any slice is parsed; the run it was cut off from ends short of its row)
+        for (int scan_level = C.slices ? 1 : 0; scan_level >= 0 && st == MP2VG_OK; scan_level--)
         for (size_t j = pic_job_begin[p]; j < pic_job_begin[p + 1] && st == MP2VG_OK; j++)  // first failing slice in stream order
-            if (outs[j].status != MP2VG_OK && !outs[j].concealed) {
+            if (outs[j].status != MP2VG_OK && !outs[j].concealed && (!scan_level || jobs[j].two)) {
                 char m[256];
                 snprintf(m, sizeof m, "picture %d slice @%llu: %s", p, (unsigned long long)jobs[j].byte_off,
                          outs[j].err.c_str());
@@ -755,6 +836,7 @@ static int scan_pass1(const uint8_t* buf, uint64_t len, const mp2vg_config_t* cf
     C.g.init(cfg->width, cfg->height, cfg->chroma_format);
     C.conceal = (cfg->reserved & MP2VG_PARSE_CONCEAL) != 0;
     C.standard = (cfg->reserved & MP2VG_PARSE_STANDARD) != 0;
+    C.slices = (cfg->reserved & MP2VG_PARSE_SLICES) != 0;
 
     double tp = now_ms();
     // ---- pass 1: start codes and headers, serially (decoder.cpp:278-329) ----
@@ -1108,6 +1190,22 @@ int parse_session_start(const uint8_t* buf, uint64_t len, const mp2vg_config_t* 
         }
         S->pic_job_begin[npics] = j;
     }
+    if (C.slices) {  // the scan's row rule: a row's slices are consecutive; coming back to a row is refused
+        std::vector<uint8_t> seen(C.mbh);
+        size_t j = 0;
+        for (int p = 0; p < npics; p++) {
+            std::fill(seen.begin(), seen.end(), 0);
+            for (size_t k = 0; k < C.pics[p].slices.size(); k++, j++) {
+                SliceJob& job = S->jobs[j];
+                const int row = slice_row_of(buf, len, job.byte_off, C.vertical_size_value > 2800);
+                job.row = row < 0 || row >= C.mbh ? -1 : row;
+                if (job.row < 0) continue;
+                job.two = seen[row] && !(k > 0 && S->jobs[j - 1].row == row && !S->jobs[j - 1].two);
+                seen[row] = 1;
+                S->row_done[(size_t)p * C.mbh + row].store(1, std::memory_order_relaxed);
+            }
+        }
+    }
     S->extra.resize(npics);
     S->damage.resize(npics);
     S->status.assign(npics, 1);
@@ -1148,7 +1246,7 @@ void parse_session_append(ParseSession* s, int p, mp2vg_mb_t* mbs_out, uint32_t*
         if (!o.coefs.empty()) memcpy(coefs_out, o.coefs.data(), o.coefs.size() * 4);
         coefs_out += o.coefs.size();
         mp2vg_mb_t* row = mbs_out + (size_t)o.mb_row * s->C.mbw;
-        for (int x = 0; x < s->C.mbw; x++) row[x].coef_off += base;
+        for (int x = o.x0; x < o.x1; x++) row[x].coef_off += base;
         base += (uint32_t)o.coefs.size();
         CoefVec().swap(o.coefs);
     };
@@ -1205,7 +1303,7 @@ extern "C" int mp2vg_parse_es(const uint8_t* buf, uint64_t len, const mp2vg_conf
             auto put = [&](SliceOut& o) {
                 if (!o.coefs.empty()) memcpy(&res->coefs[base], o.coefs.data(), o.coefs.size() * 4);
                 mp2vg_mb_t* row = res->mbs.data() + mbs_per_pic * p + (size_t)o.mb_row * C.mbw;
-                for (int x = 0; x < C.mbw; x++) row[x].coef_off += (uint32_t)base;
+                for (int x = o.x0; x < o.x1; x++) row[x].coef_off += (uint32_t)base;
                 base += o.coefs.size();
                 CoefVec().swap(o.coefs);
             };
@@ -1393,20 +1491,19 @@ extern "C" int mp2vg_scan_es(const uint8_t* buf, uint64_t len, const mp2vg_confi
         d.has_bwd = P.bwd >= 0;
         d.has_conceal_ref = C.conceal && P.conceal_ref >= 0;
         d.intra_tab = (uint8_t)(h.intra_vlc_format ? 1 : C.standard ? 0 : SP_INTRA_TAB_REFUSED);
+        d.slices = C.slices;
         S->hdr.push_back(d);
         S->pic_slice.push_back((uint32_t)S->slices.size());
         std::fill(seen.begin(), seen.end(), 0);
         for (const SliceJob& j : P.slices) {
-            // slice_vertical_position: the start code's last byte, extended by the 3 bits after it
-            // in pictures taller than 2800 lines (bytes past the buffer read as 0)
-            const int vpos = buf[j.byte_off + 3];
-            const int ext = g.vext && j.byte_off + 4 < len ? buf[j.byte_off + 4] >> 5 : 0;
-            const int row = (ext << 7) + vpos - 1;
+            const int row = slice_row_of(buf, len, j.byte_off, g.vext != 0);
             if (row < 0 || row >= C.mbh) {
                 sp_set_slice_error(p, j.byte_off, SP_R_ROW_OUTSIDE);
                 return MP2VG_E_UNSUPPORTED;
             }
-            if (seen[row]) {
+            // (MP2VG_PARSE_SLICES: the slice right after one of its row continues that row, so a row's
+            // entries are consecutive in the table; coming back to a row left earlier stays refused)
+            if (seen[row] && !(C.slices && S->slices.size() > S->pic_slice.back() && S->slices.back().mb_row == row)) {
                 sp_set_slice_error(p, j.byte_off, SP_R_TWO_SLICES);
                 return MP2VG_E_UNSUPPORTED;
             }
@@ -1489,6 +1586,7 @@ extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32
     } guard{bs};
     const uint32_t j0 = s->pic_slice[first], j1 = s->pic_slice[first + npics];
     const bool conceal = (s->cfg.reserved & MP2VG_PARSE_CONCEAL) != 0;
+    const bool slices = (s->cfg.reserved & MP2VG_PARSE_SLICES) != 0;
     std::vector<mp2vg_mb_t> scratch(mbs ? 0 : g.mbw);  // (the counts call conceals into a scratch row)
     std::vector<SpResult> res(j1 - j0);
     auto row_of = [&](const SpSlice& sl) { return mbs + per_pic * (sl.pic - first) + (uint64_t)sl.mb_row * g.mbw; };
@@ -1511,8 +1609,24 @@ extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32
             set_error("mp2vg_scan_parse_host: iteration bound exceeded");
             return MP2VG_E_STATE;
         }
-        if (conceal && r.status != MP2VG_OK && sp_reason_concealed(r.reason))
+        if (conceal && !slices && r.status != MP2VG_OK && sp_reason_concealed(r.reason))
             r.ncoef = sp_conceal_row(g, h, sl.mb_row, SpCountOut{mbs ? row_of(sl) : scratch.data()}, r.uses);
+    }
+    if (slices) {  // the row pass: start columns, cover rule on every row's run of entries, replacement rows
+        for (uint32_t j = j0; j < j1; j++) {
+            const SpSlice& sl = s->slices[j];
+            if (sl.byte_off != sl.byte_end)
+                res[j - j0].x0 = (uint16_t)sp_slice_x0(T, g, bs, (int64_t)(sl.byte_off - lo), (int64_t)(sl.byte_end - lo), (int64_t)span);
+        }
+        for (uint32_t a = j0, b; a < j1; a = b) {
+            const SpSlice& sl = s->slices[a];
+            for (b = a + 1; b < j1 && s->slices[b].pic == sl.pic && s->slices[b].mb_row == sl.mb_row;) b++;
+            if (sl.byte_off == sl.byte_end) continue;  // a missing row, concealed above
+            SpResult& r = res[a - j0];
+            sp_cover_row(&r, b - a, g.mbw, conceal);
+            if (conceal && r.status != MP2VG_OK && sp_reason_concealed(r.reason))
+                r.ncoef = sp_conceal_row(g, s->hdr[sl.pic], sl.mb_row, SpCountOut{mbs ? row_of(sl) : scratch.data()}, r.uses);
+        }
     }
     for (uint32_t j = j0; j < j1; j++)  // the first failing slice in stream order
         if (res[j - j0].status != MP2VG_OK && !(conceal && sp_reason_concealed(res[j - j0].reason))) {
@@ -1537,6 +1651,7 @@ extern "C" int mp2vg_scan_parse_host(const mp2vg_scan_t* s, int32_t first, int32
         const SpSlice& sl = s->slices[j];
         SpResult r2;
         const SpEmitOut eo{row_of(sl), coefs + base[j - j0], res[j - j0].ncoef, (uint32_t)base[j - j0]};
+        if (res[j - j0].fate == SP_FATE_DROPPED) continue;  // its row was replaced: the carrier emits it
         if (res[j - j0].reason != SP_OK) {  // a concealed row: its rebased coef_off and its DC words
             uint32_t uses;
             if (sp_conceal_row(g, s->hdr[sl.pic], sl.mb_row, eo, uses) != res[j - j0].ncoef) return MP2VG_E_STATE;

@@ -1,10 +1,13 @@
 // parse.hip — the record emitter as kernels (gfx950): elementary-stream slices in HBM -> MB
 // records and coefficient words in HBM, where recon.hip reads them.
 //
-// Mapping: one lane per slice, workgroup = one wave of 64.  The accepted subset has exactly one
-// slice per macroblock row, and the host scan has already given every slice its row, so lanes
+// Mapping: one lane per slice, workgroup = one wave of 64.  The host scan has already given every
+// slice its row, and a slice writes the records of its own columns [x0, x1) of that row (the whole
+// row without MP2VG_PARSE_SLICES, where a row has exactly one slice), so the lanes of a valid stream
 // share nothing and no atomics are needed; slices are in stream order, so a wave's lanes are
-// consecutive rows of one picture and their records are neighbours in memory.  The parser is
+// consecutive rows (or parts of rows) of one picture and their records are neighbours in memory.
+// Under MP2VG_PARSE_SLICES two slices that wrongly overlap may both store to one record; the row
+// kernel then refuses or replaces that row, so what the record holds does not matter.  The parser is
 // slice_parse.h, the very source the CPU twin (mp2vg_scan_parse_host) runs.  Lanes diverge freely
 // (a VLC parse is a data-dependent state machine); a wave costs what its slowest lane costs, and
 // occupancy across the device's waves hides that, not any cooperation inside the wave.
@@ -13,6 +16,8 @@
 // (coef_off relative to the slice) and its word count, status and reference usage; a one-
 // workgroup scan turns the counts into each slice's first word (the layout of mp2vg_parse_es:
 // slices concatenated in stream order); the emit pass parses again and writes the words there.
+// Under MP2VG_PARSE_SLICES a row is a run of table entries: a small kernel after the count pass
+// applies the cover rule to every run (sp_cover_row) and marks what breaks it.
 // Under MP2VG_PARSE_CONCEAL a small kernel between the count pass and the scan replaces the rows
 // of failed slices and of missing rows (sp_conceal_row, the one statement of the rule); the scan
 // counts them instead of reporting them, and the emit pass writes their words without parsing.
@@ -44,13 +49,49 @@ __global__ __launch_bounds__(64) void parse_count_kernel(ParseArgs a) {
     SpResult r;
     if (!slice_ok(a, s)) {  // (the host builds the table; a bad entry touches nothing, nor does an empty one)
         r.status = MP2VG_E_INVALID, r.reason = 0, r.ncoef = 0, r.fail_pos = 0, r.uses = 0, r.iters = 0;
+        r.x0 = 0, r.x1 = 0, r.fate = SP_FATE_PARSED, r.pad = 0, r.blame = 0;
         a.res[j] = r;
         return;
     }
     const SpCountOut out{a.mbs + a.mb_first[s.pic] + (size_t)s.mb_row * a.G.mbw};
     sp_parse_slice(a.T, a.G, a.hdr[s.pic], a.bs, (int64_t)s.byte_off, (int64_t)s.byte_end, (int64_t)a.span,
                    (int)s.mb_row, out, r);
+    r.x0 = 0, r.fate = SP_FATE_PARSED, r.pad = 0, r.blame = 0;  // (the row pass's fields)
     a.res[j] = r;
+}
+
+// MP2VG_PARSE_SLICES, after the count pass and before the conceal kernel and the scan, in two
+// launches.  Phase 0: every lane reads its slice's start column again (sp_slice_x0: a header and one
+// code; carrying the column through the count kernel's macroblock loop cost that kernel 30 SGPR
+// spills) and stores it in res[j].x0.  Phase 1: the lane of each row's first entry walks the row's
+// run of entries (consecutive in the table) and applies the cover rule (sp_cover_row, the one
+// statement): a cover failure goes into the blamed entry's status and reason, where the scan finds
+// it as it finds a parse failure; under MP2VG_PARSE_CONCEAL the
+// first entry becomes the row's carrier, which the conceal kernel fills like any failed slice, and
+// the others are dropped.  Every other lane returns at once.  A kernel of its own, launched under
+// the flag only, as the conceal kernel is and for its reason: the count and emit passes with the
+// flag clear are to be what they were.  An empty entry (a missing row) is a run of one and is left
+// to the conceal kernel; a bad entry ends a run, and res[] of a run is only ever touched by its
+// first lane, so the lanes share nothing.
+__global__ __launch_bounds__(64) void parse_rows_kernel(ParseArgs a, int phase) {
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= a.nslices) return;
+    const DevSlice s = a.slices[j];
+    if (!slice_ok(a, s)) return;
+    if (phase == 0) {
+        a.res[j].x0 = (uint16_t)sp_slice_x0(a.T, a.G, a.bs, (int64_t)s.byte_off, (int64_t)s.byte_end, (int64_t)a.span);
+        return;
+    }
+    if (j > 0) {
+        const DevSlice q = a.slices[j - 1];
+        if (q.pic == s.pic && q.mb_row == s.mb_row && slice_ok(a, q)) return;  // not the row's first entry
+    }
+    uint32_t n = 1;
+    for (; j + n < a.nslices; n++) {
+        const DevSlice q = a.slices[j + n];
+        if (q.pic != s.pic || q.mb_row != s.mb_row || !slice_ok(a, q)) break;
+    }
+    sp_cover_row(a.res + j, n, a.G.mbw, a.conceal != 0);
 }
 
 // MP2VG_PARSE_CONCEAL, between the count pass and the scan: a lane whose slice failed for a
@@ -134,6 +175,7 @@ __global__ __launch_bounds__(64) void parse_emit_kernel(ParseArgs a) {
     if (j >= a.nslices) return;
     const DevSlice s = a.slices[j];
     if (!entry_ok(a, s)) return;
+    if (a.res[j].fate == SP_FATE_DROPPED) return;  // MP2VG_PARSE_SLICES: its row was replaced, the carrier emits it
     const uint32_t base = a.base[j], cap = a.res[j].ncoef;
     if ((uint64_t)base + cap > a.base[a.nslices]) return;  // (never: base is the counts' prefix sum)
     const SpEmitOut out{a.mbs + a.mb_first[s.pic] + (size_t)s.mb_row * a.G.mbw, a.coefs + base, cap, base};
@@ -150,6 +192,13 @@ __global__ __launch_bounds__(64) void parse_emit_kernel(ParseArgs a) {
 hipError_t launch_parse_count(const ParseArgs& a, hipStream_t stream) {
     if (!a.nslices) return hipSuccess;
     hipLaunchKernelGGL(parse_count_kernel, dim3((a.nslices + 63) / 64), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_parse_rows(const ParseArgs& a, hipStream_t stream) {
+    if (!a.nslices || !a.rows) return hipSuccess;
+    for (int phase = 0; phase < 2; phase++)
+        hipLaunchKernelGGL(parse_rows_kernel, dim3((a.nslices + 63) / 64), dim3(64), 0, stream, a, phase);
     return hipGetLastError();
 }
 

@@ -172,8 +172,10 @@ int upload_es(mp2vg_ctx_t* c, const mp2vg_scan* scan, const mp2vg_picture_t* pic
     a.uses = S.d_uses;
     a.npics = (uint32_t)npics;
     a.conceal = conceal;
+    a.rows = (scan->cfg.reserved & MP2VG_PARSE_SLICES) != 0;
     HIPCHK(hipEventRecord(S.ev[0], st));
     HIPCHK(launch_parse_count(a, st));
+    HIPCHK(launch_parse_rows(a, st));     // (MP2VG_PARSE_SLICES only; counted with the count pass too)
     HIPCHK(launch_parse_conceal(a, st));  // (counted with the count pass in mp2vg_last_parse_times)
     HIPCHK(hipEventRecord(S.ev[1], st));
     HIPCHK(launch_parse_scan(a, (const uint32_t*)(S.d_small + o_ps), S.d_summary, st));
@@ -203,7 +205,9 @@ int upload_es(mp2vg_ctx_t* c, const mp2vg_scan* scan, const mp2vg_picture_t* pic
             const SpResult& r = S.h_all[j];
             if (r.status == MP2VG_OK) continue;
             const SpSlice& s = scan->slices[j0 + j];
-            S.damage.push_back({s.pic - first, s.mb_row, r.status, r.reason, s.byte_off});
+            // (MP2VG_PARSE_SLICES: the row's first entry carries the damage, the blamed one names the offset)
+            const uint32_t jb = j + r.blame < ns ? j + r.blame : j;
+            S.damage.push_back({s.pic - first, s.mb_row, r.status, r.reason, scan->slices[j0 + jb].byte_off});
         }
         for (int32_t i = 0; i < npics; i++)  // (bit 2 of the scan kernel's per-picture word: a concealed row)
             if ((S.h_uses[i] & 4) && retyped[i].picture_coding_type == 1 && scan->hdr[first + i].has_conceal_ref)

@@ -32,10 +32,14 @@ struct ParseArgs {
     uint32_t* uses;          // per picture: bit 0 forward, bit 1 backward (scan)
     uint32_t npics;
     uint32_t conceal;        // MP2VG_PARSE_CONCEAL: failed slices and missing rows become replacement rows
+    uint32_t rows;           // MP2VG_PARSE_SLICES: a row has a run of entries; the row kernel applies the cover rule
 };
 
 // workgroup = one wave of 64 lanes, lane = slice
 hipError_t launch_parse_count(const ParseArgs& a, hipStream_t stream);
+// MP2VG_PARSE_SLICES (a.rows; otherwise nothing is launched): after the count pass, before the
+// conceal kernel and the scan
+hipError_t launch_parse_rows(const ParseArgs& a, hipStream_t stream);
 // MP2VG_PARSE_CONCEAL (a.conceal; otherwise nothing is launched): after the count pass, before the scan
 hipError_t launch_parse_conceal(const ParseArgs& a, hipStream_t stream);
 // pic_slice[npics + 1]: each picture's slice range; summary[3]: total words, first failing slice

@@ -58,6 +58,8 @@ enum {
     SP_R_RUN_PAST_63,
     SP_R_OVERRUN,
     SP_R_ROW_NOT_WHOLE,
+    SP_R_ROW_GAP,           // MP2VG_PARSE_SLICES: the row's slices leave columns uncovered (sp_cover_row)
+    SP_R_ROW_OVERLAP,       // MP2VG_PARSE_SLICES: a slice starts before the one in front of it ended
     SP_R_COUNT
 };
 
@@ -86,6 +88,8 @@ inline const char* sp_reason_text(int r) {
     case SP_R_RUN_PAST_63: return "coefficient run past position 63";
     case SP_R_OVERRUN: return "slice overruns the buffer";
     case SP_R_ROW_NOT_WHOLE: return "slice does not cover the whole macroblock row";
+    case SP_R_ROW_GAP: return "slices of a macroblock row leave a gap";
+    case SP_R_ROW_OVERLAP: return "slices of a macroblock row overlap or are out of order";
     default: return "";
     }
 }
@@ -110,7 +114,10 @@ struct SpPicHdr {  // the per-picture device header
     // (intra_vlc_format 1), 0 = B.14 (intra_vlc_format 0 under MP2VG_PARSE_STANDARD), SP_INTRA_TAB_REFUSED
     // = intra_vlc_format 0 without the flag.  The one byte the parser reads of the two settings.
     uint8_t intra_tab;
-    uint8_t reserved[2];
+    // MP2VG_PARSE_SLICES, filled by the scan: 1 = a slice starts at the column its first
+    // macroblock_address_increment names and ends where its macroblock loop ends (the rule below)
+    uint8_t slices;
+    uint8_t reserved[1];
 };  // 16 bytes
 static_assert(sizeof(SpPicHdr) == 16, "SpPicHdr is the 16-byte per-picture device header");
 
@@ -130,7 +137,25 @@ struct SpResult {  // per slice
     uint32_t fail_pos;  // reader byte position (from the slice's start code) at the rejection
     uint32_t uses;      // bit 0: a macroblock predicts forward, bit 1: backward
     uint32_t iters;     // loop iterations (bounded by sp_iter_bound)
-};  // 24 bytes
+    // the slice wrote records [x0, x1) of its row.  x1: the column after its last record (mbw of a
+    // whole-row slice; the column of the rejection in a failed one)
+    uint32_t x1;
+    // MP2VG_PARSE_SLICES, set by the row pass (sp_slice_x0, sp_cover_row; 0 without it): the slice's
+    // start column, what the emit pass does with the entry, and, of a replacement carrier, the
+    // blamed entry, counted from the carrier.  The parse itself sets none of the four: keeping the
+    // start column through the macroblock loop cost the count kernel 30 SGPR spills.
+    uint16_t x0;
+    uint8_t fate;
+    uint8_t pad;
+    uint32_t blame;
+};  // 36 bytes
+
+// SpResult.fate
+enum {
+    SP_FATE_PARSED = 0,   // the emit pass parses the slice (or, with a reason set and the flag clear, conceals its row)
+    SP_FATE_CARRIER = 1,  // first entry of a replaced row: it owns the replacement row and its words
+    SP_FATE_DROPPED = 2   // another entry of a replaced row: no words, and the emit pass writes nothing
+};
 
 // Upper bound on the loop iterations of one slice of `bytes` bytes.  The reader position is at
 // most 8 bytes past the slice's end when a macroblock starts (the host's overrun test); one
@@ -325,12 +350,22 @@ struct SpNullOut {
         res.fail_pos = (uint32_t)(br.p - br.base); \
         res.uses = uses;                         \
         res.iters = iters;                       \
+        res.x1 = (uint32_t)x;                    \
         return;                                  \
     } while (0)
 
 // One slice.  buf + [off, end) is the slice (start code first), bytes at or past hend read as 0.
 // The slice's row comes from the slice table (the scan read and checked it): the header's row
 // bits are skipped here.
+//
+// MP2VG_PARSE_SLICES (h.slices), the rule for a slice that is a part of its row: the slice's first
+// macroblock_address_increment (escapes included) names its start column x0 = increment - 1.  It is
+// no skip run: no records are written for it, it is legal in an I picture, and it resets nothing (the
+// predictors and the quantiser scale start from the slice header as ever).  x0 >= mbw is "macroblock
+// beyond the end of the row".  The slice ends at the column x1 where its macroblock loop ends;
+// SP_R_NOT_COLUMN0 and SP_R_ROW_NOT_WHOLE are not produced, and whether the row's slices tile
+// [0, mbw) is sp_cover_row's to say.  The slice writes records [x0, x1) only.  res.x1 is set here,
+// res.x0 by the row pass (sp_slice_x0 reads the increment again).
 template <class Out>
 SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h, const uint8_t* buf, int64_t off,
                           int64_t end, int64_t hend, int mb_row, const Out& out, SpResult& res) {
@@ -377,7 +412,14 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
         const int e = sp_vlc(br, w + T.mba, 11);
         if (e < 0 || e >= 33) SP_FAIL(MP2VG_E_BITSTREAM, SP_R_BAD_MBA);
         inc += (int)w[T.mba_val + e];
-        if (x == 0 && inc != 1) SP_FAIL(MP2VG_E_UNSUPPORTED, SP_R_NOT_COLUMN0);
+        // (x is 0 at a slice's first macroblock only.)  MP2VG_PARSE_SLICES: the slice's first increment is
+        // its start column, not a skip run: x moves there (at most to mbw, which the test after the skip
+        // run refuses) and the increment counts as 1.  Selects, not a branch of its own.
+        const bool start = x == 0 && h.slices;
+        if (x == 0 && inc != 1 && !start) SP_FAIL(MP2VG_E_UNSUPPORTED, SP_R_NOT_COLUMN0);
+        const uint32_t ahead = (uint32_t)(inc - 1) < (uint32_t)mbw ? (uint32_t)(inc - 1) : (uint32_t)mbw;
+        x += start ? (int)ahead : 0;
+        inc = start ? 1 : inc;
         if (inc > 1) {
             if (pct == 1) SP_FAIL(MP2VG_E_UNSUPPORTED, SP_R_SKIP_IN_I);
             if (pct == 2)
@@ -628,7 +670,7 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
         previous_mb_type = mbt;
         x++;
     } while (br.peek(23) != 0);
-    if (x != mbw) SP_FAIL(MP2VG_E_UNSUPPORTED, SP_R_ROW_NOT_WHOLE);
+    if (x != mbw && !h.slices) SP_FAIL(MP2VG_E_UNSUPPORTED, SP_R_ROW_NOT_WHOLE);
     SP_FAIL(MP2VG_OK, SP_OK);
 }
 
@@ -638,7 +680,86 @@ SP_HD void sp_parse_slice(const SpTables& T, const SpGeom& G, const SpPicHdr& h,
 // A slice that failed for one of these reasons, or a row no slice covers, is replaced as a whole
 // row.  SP_R_ROW_OUTSIDE and SP_R_TWO_SLICES stay rejections: such a slice names no row of its own.
 SP_HD bool sp_reason_concealed(int reason) {
-    return reason == SP_R_ROW_UNCOVERED || (reason >= SP_R_MB_BEYOND_ROW && reason <= SP_R_ROW_NOT_WHOLE);
+    return reason == SP_R_ROW_UNCOVERED || (reason >= SP_R_MB_BEYOND_ROW && reason <= SP_R_ROW_OVERLAP);
+}
+
+// ---- row pass (MP2VG_PARSE_SLICES) ----------------------------------------------------------------
+// The start column of a slice: its header and its first macroblock_address_increment read again,
+// exactly as sp_parse_slice reads them.  At most mbw; 0 where the increment's code is invalid (the
+// parse has failed the slice there, and a failed slice's columns are never looked at).
+SP_HD uint32_t sp_slice_x0(const SpTables& T, const SpGeom& G, const uint8_t* buf, int64_t off, int64_t end, int64_t hend) {
+    SpReader br;
+    br.init(buf, off, end, hend);
+    br.skip(24);
+    (void)br.read(8);
+    if (G.vext) (void)br.read(3);
+    (void)br.read(5);
+    if (br.peek(1) == 1) {
+        br.skip(1 + 1 + 1 + 6);
+        while (br.peek(1) == 1) br.skip(9);  // (ends in the zeros of the next start code or past the buffer)
+    }
+    br.skip(1);
+    uint32_t inc = 0;
+    while (br.peek(11) == 0x008) {
+        br.skip(11);
+        inc += 33;
+    }
+    const int e = sp_vlc(br, T.w + T.mba, 11);
+    if (e < 0 || e >= 33) return 0;
+    inc += T.w[T.mba_val + e];
+    return inc - 1 < (uint32_t)G.mbw ? inc - 1 : (uint32_t)G.mbw;
+}
+
+// ---- row cover (MP2VG_PARSE_SLICES): the one statement of the rule ----------------------------
+// r[0 .. n) are the count pass's results of the slices of one macroblock row, in table order (the
+// scan keeps a row's entries consecutive).  They must tile [0, mbw): the first starts at column 0,
+// each next one where the one before it ended, the last ends at mbw.  The row breaks at its first
+// entry, in table order, that failed its parse, starts past the expected column (SP_R_ROW_GAP) or
+// before it (SP_R_ROW_OVERLAP); a row whose entries all fit but end short breaks at its last entry
+// (SP_R_ROW_GAP).  That entry is blamed: a cover failure is written into its status and reason
+// (MP2VG_E_UNSUPPORTED), a parse failure is there already.
+// Under MP2VG_PARSE_CONCEAL a row that breaks for a concealable reason is replaced as a whole: its
+// first entry becomes the carrier (the blamed entry's status, reason and fail_pos, blame = its
+// distance), which the conceal step fills with sp_conceal_row as it does any failed slice; every
+// other entry is dropped (status OK, no words, nothing to emit).
+SP_HD void sp_cover_row(SpResult* r, uint32_t n, int mbw, bool conceal) {
+    uint32_t blame = n;
+    int32_t status = MP2VG_OK, reason = SP_OK;
+    int expect = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        if (r[k].status != MP2VG_OK) {
+            blame = k, status = r[k].status, reason = r[k].reason;
+            break;
+        }
+        const int x0 = (int)r[k].x0;
+        if (x0 != expect) {
+            blame = k, status = MP2VG_E_UNSUPPORTED, reason = x0 > expect ? SP_R_ROW_GAP : SP_R_ROW_OVERLAP;
+            break;
+        }
+        expect = (int)r[k].x1;
+    }
+    if (blame == n) {
+        if (expect == mbw) return;
+        blame = n - 1, status = MP2VG_E_UNSUPPORTED, reason = SP_R_ROW_GAP;
+    }
+    if (!(conceal && sp_reason_concealed(reason))) {
+        r[blame].status = status;
+        r[blame].reason = reason;
+        return;
+    }
+    const uint32_t fail_pos = r[blame].fail_pos;
+    for (uint32_t k = 1; k < n; k++) {
+        r[k].status = MP2VG_OK;
+        r[k].reason = SP_OK;
+        r[k].ncoef = 0;
+        r[k].uses = 0;
+        r[k].fate = SP_FATE_DROPPED;
+    }
+    r[0].status = status;
+    r[0].reason = reason;
+    r[0].fail_pos = fail_pos;
+    r[0].fate = SP_FATE_CARRIER;
+    r[0].blame = blame;
 }
 
 // The replacement row of picture h, through an output policy (the parser's: SpCountOut writes the

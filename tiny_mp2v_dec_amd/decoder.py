@@ -57,12 +57,14 @@ class decoder_config_t:  # noqa: N801  (reference name)
     device_parse: bool = False  # MP2VG_DECODER_DEVICE_PARSE: slices parsed on the device, no parse workers
     conceal: bool = False  # MP2VG_PARSE_CONCEAL: damaged rows are replaced, decode() goes on
     standard: bool = False  # MP2VG_PARSE_STANDARD: the standard's matrix rule, intra_vlc_format = 0
+    slices: bool = False  # MP2VG_PARSE_SLICES: any number of slices per macroblock row
 
 
 MP2VG_DECODER_DEVICE_FRAMES = 1  # include/mp2vg.h
 MP2VG_DECODER_DEVICE_PARSE = 4
 MP2VG_PARSE_CONCEAL = 8
 MP2VG_PARSE_STANDARD = 16
+MP2VG_PARSE_SLICES = 32
 _hip = None
 
 
@@ -195,7 +197,8 @@ class mp2v_decoder_c:  # noqa: N801  (reference name)
         self._cfg.reserved = ((MP2VG_DECODER_DEVICE_FRAMES if self._device else 0) |
                               (MP2VG_DECODER_DEVICE_PARSE if config.device_parse else 0) |
                               (MP2VG_PARSE_CONCEAL if config.conceal else 0) |
-                              (MP2VG_PARSE_STANDARD if config.standard else 0))
+                              (MP2VG_PARSE_STANDARD if config.standard else 0) |
+                              (MP2VG_PARSE_SLICES if config.slices else 0))
         self._error = None
 
         def _cb(user, fptr):

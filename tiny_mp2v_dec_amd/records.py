@@ -80,13 +80,14 @@ class Parsed:
     conceal=True (MP2VG_PARSE_CONCEAL, include/mp2vg.h): damaged slices and missing rows are
     replaced row by row instead of failing the parse; .damage lists them (_lib.DAMAGE_DTYPE).
     standard=True (MP2VG_PARSE_STANDARD): quantiser matrices from the sequence header, the
-    defaults and partial extensions as the standard rules them, and intra_vlc_format = 0."""
+    defaults and partial extensions as the standard rules them, and intra_vlc_format = 0.
+    slices=True (MP2VG_PARSE_SLICES): any number of slices per macroblock row."""
 
     def __init__(self, es: bytes, width, height, chroma_format, threads=0, reordering=True, conceal=False,
-                 standard=False):
+                 standard=False, slices=False):
         self.width, self.height, self.chroma_format = width, height, chroma_format
         cfg = _lib.make_config(width, height, chroma_format, threads=threads, reordering=reordering,
-                               flags=_lib.parse_flags(conceal, standard))
+                               flags=_lib.parse_flags(conceal, standard, slices))
         buf = np.frombuffer(es, dtype=np.uint8)
         h = ctypes.c_void_p()
         check(lib().mp2vg_parse_es(buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
@@ -128,14 +129,17 @@ class Scan:
     (MP2VG_PARSE_CONCEAL): the scan lets missing rows through and carries the flag to parse_host and
     DeviceContext.upload_es, which replace damaged rows; the damage of an upload is
     DeviceContext.last_damage().  standard=True (MP2VG_PARSE_STANDARD) as for Parsed; the scan
-    carries it to parse_host and DeviceContext.upload_es too."""
+    carries it to parse_host and DeviceContext.upload_es too.  slices=True (MP2VG_PARSE_SLICES)
+    likewise: a row's slices are consecutive entries of the slice table."""
 
-    def __init__(self, es: bytes, width, height, chroma_format, reordering=True, conceal=False, standard=False):
+    def __init__(self, es: bytes, width, height, chroma_format, reordering=True, conceal=False, standard=False,
+                 slices=False):
         self.width, self.height, self.chroma_format = width, height, chroma_format
         self.conceal = bool(conceal)
         self.standard = bool(standard)
+        self.slices = bool(slices)
         cfg = _lib.make_config(width, height, chroma_format, reordering=reordering,
-                               flags=_lib.parse_flags(conceal, standard))
+                               flags=_lib.parse_flags(conceal, standard, slices))
         self._buf = np.frombuffer(es, dtype=np.uint8)
         self.h = ctypes.c_void_p()
         check(lib().mp2vg_scan_es(self._buf.ctypes.data_as(ctypes.c_void_p), len(es), ctypes.byref(cfg),
@@ -618,8 +622,9 @@ def pixel_aspect(headers):
 stream_pixel_aspect = pixel_aspect  # for functions with a `pixel_aspect` argument
 
 
-def _open_stream(es, width, height, chroma_format, device_parse, conceal, standard=False):
-    return (Scan if device_parse else Parsed)(es, width, height, chroma_format, conceal=conceal, standard=standard)
+def _open_stream(es, width, height, chroma_format, device_parse, conceal, standard=False, slices=False):
+    return (Scan if device_parse else Parsed)(es, width, height, chroma_format, conceal=conceal, standard=standard,
+                                              slices=slices)
 
 
 def probe(es):
@@ -649,7 +654,7 @@ def _make_resident(ctx, parsed, device_parse):
 
 
 def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear", matrix=None, device=0,
-               device_parse=False, conceal=False, return_damage=False, standard=False):
+               device_parse=False, conceal=False, return_damage=False, standard=False, slices=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one torch.uint8 RGB tensor on cuda:<device>, cropped to the sequence header's
     horizontal_size_value x vertical_size_value when these are set and no larger than the coded
@@ -660,8 +665,9 @@ def decode_rgb(es, width, height, chroma_format, layout="nchw", chroma="linear",
     DeviceContext.upload_es) instead of uploading host-parsed records; the result is the same.
     conceal=True decodes a damaged stream (MP2VG_PARSE_CONCEAL: damaged rows are replaced instead of
     failing the call); return_damage=True returns (tensor, damage), damage as Parsed.damage.
-    standard=True (MP2VG_PARSE_STANDARD) admits streams of ordinary encoders, as for Parsed."""
-    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal, standard)
+    standard=True (MP2VG_PARSE_STANDARD) admits streams of ordinary encoders, as for Parsed;
+    slices=True (MP2VG_PARSE_SLICES) any number of slices per macroblock row."""
+    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal, standard, slices)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     size = (w, h) if 0 < w <= width and 0 < h <= height else None
@@ -726,7 +732,8 @@ def field_plan(display, flags, fields):
 
 def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="float16", mean=None, std=None,
                   layout="nchw", chroma="linear", matrix=None, device=0, device_parse=False, fields=None, fit=None,
-                  pad=(0, 0, 0), pixel_aspect="stream", conceal=False, return_damage=False, standard=False):
+                  pad=(0, 0, 0), pixel_aspect="stream", conceal=False, return_damage=False, standard=False,
+                  slices=False):
     """Decode a whole elementary stream (coded size width x height) and return its pictures in
     display order as one model-input tensor on cuda:<device> (DeviceContext.export_tensor: size,
     dtype, mean / std, layout and chroma as there).  crop=None takes the sequence header's
@@ -749,8 +756,8 @@ def decode_tensor(es, width, height, chroma_format, size, crop=None, dtype="floa
     own (records.pixel_aspect; a stream whose aspect code gives none raises Mp2vgError, it is not
     guessed at), a tuple (n, d) overrides it.
 
-    conceal, return_damage and standard as in decode_rgb."""
-    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal, standard)
+    conceal, return_damage, standard and slices as in decode_rgb."""
+    parsed = _open_stream(es, width, height, chroma_format, device_parse, conceal, standard, slices)
     sh = parsed.headers.sequence_header
     w, h = int(sh.horizontal_size_value), int(sh.vertical_size_value)
     if crop is None and 0 < w <= width and 0 < h <= height:
@@ -835,7 +842,8 @@ def reference_distances(pics, display):
     return np.where(ref >= 0, pos[np.maximum(ref, 0)] - here, 0).astype(np.int32)
 
 
-def decode_motion(es, width, height, chroma_format, parse="device", device=0, conceal=False, standard=False):
+def decode_motion(es, width, height, chroma_format, parse="device", device=0, conceal=False, standard=False,
+                  slices=False):
     """The motion field and block activity of a whole elementary stream in display order, with no
     reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
     parse (parse="host": Parsed, upload) the stream, make it resident and export
@@ -849,7 +857,7 @@ def decode_motion(es, width, height, chroma_format, parse="device", device=0, co
         raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
     import torch
     torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
-    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal, standard)
+    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal, standard, slices)
     if not parsed.npics:
         raise ValueError("the stream has no pictures")
     with DeviceContext(width, height, chroma_format, slots=parsed.npics, device=device) as ctx:
@@ -892,7 +900,7 @@ def residual_host(pics, mbs, coefs, width, height, chroma_format, order=None, dt
 
 
 def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int16", chroma=True, zero_intra=False,
-                    parse="device", device=0, conceal=False, standard=False):
+                    parse="device", device=0, conceal=False, standard=False, slices=False):
     """The coded prediction error of an elementary stream's pictures in display order, with no
     reconstruction: scan (parse="device": slices parsed on the device, DeviceContext.upload_es) or
     parse (parse="host": Parsed, upload) the stream, make it resident and export once
@@ -907,7 +915,7 @@ def decode_residual(es, width, height, chroma_format, pictures=None, dtype="int1
         raise ValueError(f"parse {parse!r}: expected 'device' or 'host'")
     import torch
     torch.cuda.init()  # torch's runtime before the context's first HIP call, as in decode_rgb
-    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal, standard)
+    parsed = _open_stream(es, width, height, chroma_format, parse == "device", conceal, standard, slices)
     if not parsed.npics:
         raise ValueError("the stream has no pictures")
     display = np.asarray(parsed.display, np.int32)
